@@ -5,6 +5,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+A plain run prints the headline only: set-up, warm-up, the K timed steps (`ms_per_step`, `value`), the outputs of the last
+step with --dump-outputs DIR, one JSON line.  `--full` adds every context leg listed below (they run after the headline).
+
 One "step" = one forward render of the whole frame (preprocess -> depth sort -> scan -> emit -> tile sort -> ranges
 -> blend, including the 8-byte num_rendered read-back) of the synthetic stand-in for configs[1] ("garden", ~1 M
 Gaussians, 1080p): P = 1e6, 1920x1080, SURVEY.md 8(d) generator, seed 0, s_med 0.012.  The library bins every Gaussian into
@@ -18,7 +21,7 @@ value = W*H / (max-over-ranks time per frame).  If a collective of that mode is 
 run falls back to mode B (replicated parameters, bands only) and says so in the line; any other failure still prints a JSON
 line with an "error" field.
 
-The JSON line also carries
+With --full the JSON line also carries
   train_iters_per_s : forward + loss + backward + Adam on all parameters, a NEW CAMERA EVERY ITERATION (train.py:96-102:
                       --views synthetic cameras around the generating one, cycled), steps/s; legs for the dense fused Adam,
                       for the reference's accelerated call form (SparseGaussianAdam + separate SH tensors,
@@ -101,7 +104,15 @@ def parse():
                     "measure roofline.traffic in this run")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)      # the short workload those child runs profile
     ap.add_argument("--cpu-workers", type=int, default=0, help="worker processes of the CPU baseline's blend (0 = all host cores)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every context leg after the headline (event pass, frames in flight, stage "
+                    "table and counters, reference tile rectangles, tracking build, train legs, other configs, CPU baseline, full training "
+                    "loop, PMC child runs, rooflines); without it the run sets up, warms up, times the --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed frame returned (color, radii, invdepth; "
+                    "rank 0's assembled color with N > 1) to DIR/<name>.npy as float32; above 64 MB in all, a fixed seeded sample of each")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def algorithmic_bytes(P, V, R, T, npix, M=16, track=False):
@@ -136,6 +147,27 @@ def make_views(make_camera, look_at_camera, W, H, n):
         r = 0.25 + 0.35 * ((k * 7) % 5) / 4.0
         cams.append(look_at_camera(W, H, (r * math.cos(ang), r * math.sin(ang), -0.2 * ((k % 3) - 1)), (0.0, 0.0, 7.0)))
     return cams
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as float32 to out_dir/<name>.npy (integer outputs such as radii are exact in float32).  When the
+    arrays hold more than DUMP_LIMIT_BYTES in all, each is replaced by the same fraction of its elements, flattened, at sorted
+    positions drawn from a generator seeded with DUMP_SAMPLE_SEED -- identical from run to run for the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    frac = min(1.0, (DUMP_LIMIT_BYTES - 1024 * len(arrays)) / max(1, total))      # (1 KiB per file for the .npy header)
+    for name, t in sorted(arrays.items()):
+        t = t.detach().float().cpu()
+        if frac < 1.0:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(t.numel(), generator=g)[:int(t.numel() * frac)].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
 
 
 def main():
@@ -184,6 +216,7 @@ def _run(a):
 
     from gsr_synth import look_at_camera, make_camera, make_scene, make_clustered_scene
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _lib, rasterize_gaussians
+    import diff_gaussian_rasterization as _dgr
     from diff_gaussian_rasterization.debug import forward_with_views
     from diff_gaussian_rasterization.parallel import (BandPlan, gather_strips_async, row_costs_from_ranges, probe_collectives,
                                                      set_exact_strips, sharded_forward_begin, sharded_forward_finish)
@@ -209,19 +242,24 @@ def _run(a):
     gx, gy = (W + 15) // 16, (H + 15) // 16
     npix = W * H
 
-    # ---- scene statistics (V, R) + band plan from a dry run ----
-    with torch.no_grad():
-        v0 = forward_with_views(rs, sc.means3D, sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
-        V = int((v0["radii"] > 0).sum())
-        R = int(v0["R"])
-        row_cost = row_costs_from_ranges(v0["ranges"].long(), gx, gy, banded=False)   # full frame on every rank
-        del v0
+    # ---- scene statistics (V, R) + band plan from a dry run (a plain single-GPU run takes V and R from its last timed frame) ----
+    snug_opt = int(dict(o.split("=") for o in a.opt).get("snug_tiles", 1))      # (an A/B run may have switched it off)
+    V = R = R_reference = row_cost = None
+    full_setup = a.full or a.pmc_child          # (the PMC child profiles the same launches as before: the dry runs included)
+    if full_setup or world > 1:
+        with torch.no_grad():
+            v0 = forward_with_views(rs, sc.means3D, sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
+            V = int((v0["radii"] > 0).sum())
+            R = int(v0["R"])
+            row_cost = row_costs_from_ranges(v0["ranges"].long(), gx, gy, banded=False)   # full frame on every rank
+            del v0
+    if full_setup:
         # the instances the REFERENCE would bin (tile square of radius 3 sqrt(lambda_max)); the product bins the snug rectangle of
         # the alpha >= 1/255 ellipse -- same outputs bit for bit (tests/test_gpu_parity.py::test_snug_tiles_change_no_bit)
-        snug_opt = int(dict(o.split("=") for o in a.opt).get("snug_tiles", 1))      # (an A/B run may have switched it off)
         _lib.set_option("snug_tiles", 0)
         try:
-            R_reference = int(forward_with_views(rs, sc.means3D, sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)["R"])
+            with torch.no_grad():
+                R_reference = int(forward_with_views(rs, sc.means3D, sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)["R"])
         finally:
             _lib.set_option("snug_tiles", snug_opt)
     plan = BandPlan.uniform(gy, world) if (a.uniform_bands or world == 1) else BandPlan.balanced(row_cost, world)
@@ -273,31 +311,43 @@ def _run(a):
     # beside kernels of the neighbouring frames.  Every frame is complete (assembled on every rank) before the closing
     # barrier of the timed region.
     in_flight, pending = [], []
+    # --dump-outputs: what the LAST timed frame returned is kept (frame number capture_at; no reference is held for the other frames).
+    # N > 1: frames complete in the order they were issued, so the capture_at-th assembled image is that frame's.
+    fwd_n, done_n, capture_at, last_out = [0], [0], [0], {}
+
+    def keep_image(img):
+        done_n[0] += 1
+        if done_n[0] == capture_at[0]:
+            last_out["color"] = img
+        return img
 
     def forward_step():
+        fwd_n[0] += 1
         with torch.no_grad():
             if mode == "C":
                 pending.append(sharded_forward_begin(rs, *shard, plan))
                 if len(pending) > 1:
                     in_flight.append(sharded_forward_finish(pending.pop(0)))
                     if len(in_flight) > 1:
-                        return in_flight.pop(0).wait()
+                        return keep_image(in_flight.pop(0).wait())
                 return None
             if mode == "A":      # record all-gather -> every rank bins its band -> strip all-gather (one frame at a time)
-                return _two_axis(rs, *shard, plan, P_pad_fwd)[0]
+                return keep_image(_two_axis(rs, *shard, plan, P_pad_fwd)[0])
             color, radii, invd = rasterize_gaussians(sc.means3D, None, sc.shs, None, sc.opacities, sc.scales,
                                                      sc.rotations, None, rs, band)
             if world > 1:
                 in_flight.append(gather_strips_async(color, plan, H))
                 if len(in_flight) > 1:
-                    color = in_flight.pop(0).wait()
+                    color = keep_image(in_flight.pop(0).wait())
+            elif fwd_n[0] == capture_at[0]:
+                last_out.update(color=color, radii=radii, invdepth=invd, num_rendered=_dgr._last_R)
         return color
 
     def drain():
         while pending:
             in_flight.append(sharded_forward_finish(pending.pop(0)))
         while in_flight:
-            in_flight.pop(0).wait()
+            keep_image(in_flight.pop(0).wait())
 
     def sync_all():
         drain()
@@ -317,6 +367,7 @@ def _run(a):
     retimed = {}
 
     event_stats = {}
+    frames_timed = {}
     last_gaps = {}      # leg -> host-side step intervals of its last timed pass (the host is paced by the per-frame R read-back)
 
     # The timed region holds the K steps and nothing else.  Rounds 1-4 also recorded a HIP event after every step inside it; an event is
@@ -330,11 +381,13 @@ def _run(a):
             sync_all()
             t0 = time.perf_counter()
             stamps = [t0]
+            f0 = fwd_n[0]
             for i in range(n):
                 step()
                 stamps.append(time.perf_counter())
             sync_all()
             dt = time.perf_counter() - t0
+            frames_timed[name] = fwd_n[0] - f0      # forward_step calls between the two synchronisations that bound the timed region
             gaps = [b - a for a, b in zip(stamps[:-1], stamps[1:])]
             last_gaps[name] = gaps
             gmax = max(gaps) * 1e3 if gaps else 0.0
@@ -345,7 +398,7 @@ def _run(a):
                 break
             retimed[name] = retimed.get(name, 0) + 1
         per = []
-        if n > 0 and (name in EVENT_PASS_LEGS or name.startswith("other_configs")):      # the instrumented pass (not part of any reported rate)
+        if n > 0 and a.full and (name in EVENT_PASS_LEGS or name.startswith("other_configs")):      # the instrumented pass (not part of any reported rate)
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
             evs[0].record()
             for i in range(n):
@@ -374,7 +427,9 @@ def _run(a):
             for _ in range(10):
                 step()
         # (VERDICT r05 weak #10b: the stall re-time stays OFF the leg `value` comes from; its largest step gap is reported instead)
+        capture_at[0] = fwd_n[0] + a.steps          # the last of the timed frames
         r_ = timed_loop(step, a.steps, "forward", stall_check=False)
+        capture_at[0] = 0
         forward_gap[0] = r_[1]
         return r_[0]
 
@@ -403,6 +458,43 @@ def _run(a):
         dt = timed_forward(forward_step_streams)
     ms_per_step = dt / a.steps * 1e3
     mpix_s = npix / (dt / a.steps) / 1e6
+    if world == 1 and V is None:              # (plain run: no dry run, the last timed frame says it)
+        V, R = int((last_out["radii"] > 0).sum()), int(last_out["num_rendered"])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {k: v for k, v in last_out.items() if torch.is_tensor(v)})
+    last_out.clear()
+
+    def run_config():                         # (read again at the end of a --full run: the exchange counters grow with every leg)
+        return {"workload": "configs[1] stand-in: 1M random Gaussians (SURVEY 8(d) generator, seed %d, s_med %.4g), "
+                            "%dx%d forward render, SH degree 3" % (a.seed, a.s_med, W, H),
+                "P": P, "visible": V, "num_rendered": R, "num_rendered_reference_tile_squares": R_reference, "tiles": gx * gy,
+                "parallelism": ("one GPU" if world == 1 else
+                                ("mode C x%d: Gaussians sharded (P/N per rank) + tile-row bands%s; 48-byte packed splat records sent only to "
+                                 "the bands they touch (all_to_all_single), strips all-gathered; frames pipelined two deep" if mode == "C" else
+                                 "mode A x%d: Gaussians sharded (P/N per rank) + tile-row bands%s; all-gather of the projected 64-byte records, strips "
+                                 "all-gathered, reduce-scatter of the 48-byte gradient rows (north_star's partitioning verbatim)" if mode == "A" else
+                                 "mode B x%d: replicated parameters, tile-row bands%s, strip all-gather of frame i overlapped with frame i+1")
+                                % (world, " (uniform)" if a.uniform_bands else " (instance-balanced)")),
+                "mode": mode, "collectives": collectives,
+                "exchange": None if exch is None else {"form": exch.mode, "capacity": exch.capacity, "frames_exact": exch.frames_exact,
+                                                       "frames_fixed": exch.frames_fixed, "overflows": exch.overflows},
+                "render_fwd_variant": a.variant or 0, "options": os.environ.get("GSR_OPTIONS", ""),
+                "frame_streams": n_streams,
+                "frame_streams_note": "value = frames / time with consecutive frames alternating between HIP streams "
+                                      "(double-buffered); frame_latency_ms = one frame after the other on one stream"
+                                      if n_streams > 1 else "one frame after the other on one stream"}
+    if not a.full:
+        if rank == 0:
+            print(json.dumps({"metric": "Mpix/s forward (1 M Gaussians @1080p); train iters/s alongside",
+                              "value": round(mpix_s, 2), "unit": "Mpix/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                              "ms_per_step": round(ms_per_step, 4), "frame_latency_ms": round(latency_ms, 4), "timed_frames": frames_timed["forward"],
+                              "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                              "forward_max_step_gap_ms": round(forward_gap[0], 3), "config": run_config(),
+                              "note": "headline only: the train legs, stage table, rooflines and other context legs run with --full"}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # for context only (NOT `value`): independent frames in flight on three HIP streams -- what a loop over a camera list can do
     # (render.py:37-46 renders view after view, no frame depends on another).  Half of a frame's 11 launches are small latency-bound
@@ -1322,24 +1414,7 @@ def _run(a):
             "ms_per_step": round(ms_per_step, 4), "frame_latency_ms": round(latency_ms, 4),
             "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic", "parity": "oracle-only (the reference rasterizer is an un-vendored submodule)",
-            "config": {"workload": "configs[1] stand-in: 1M random Gaussians (SURVEY 8(d) generator, seed %d, s_med %.4g), "
-                                   "%dx%d forward render, SH degree 3" % (a.seed, a.s_med, W, H),
-                       "P": P, "visible": V, "num_rendered": R, "num_rendered_reference_tile_squares": R_reference, "tiles": gx * gy,
-                       "parallelism": ("one GPU" if world == 1 else
-                                       ("mode C x%d: Gaussians sharded (P/N per rank) + tile-row bands%s; 48-byte packed splat records sent only to "
-                                        "the bands they touch (all_to_all_single), strips all-gathered; frames pipelined two deep" if mode == "C" else
-                                        "mode A x%d: Gaussians sharded (P/N per rank) + tile-row bands%s; all-gather of the projected 64-byte records, strips "
-                                        "all-gathered, reduce-scatter of the 48-byte gradient rows (north_star's partitioning verbatim)" if mode == "A" else
-                                        "mode B x%d: replicated parameters, tile-row bands%s, strip all-gather of frame i overlapped with frame i+1")
-                                       % (world, " (uniform)" if a.uniform_bands else " (instance-balanced)")),
-                       "mode": mode, "collectives": collectives,
-                       "exchange": None if exch is None else {"form": exch.mode, "capacity": exch.capacity, "frames_exact": exch.frames_exact,
-                                                              "frames_fixed": exch.frames_fixed, "overflows": exch.overflows},
-                       "render_fwd_variant": a.variant or 0, "options": os.environ.get("GSR_OPTIONS", ""),
-                       "frame_streams": n_streams,
-                       "frame_streams_note": "value = frames / time with consecutive frames alternating between HIP streams "
-                                             "(double-buffered); frame_latency_ms = one frame after the other on one stream"
-                                             if n_streams > 1 else "one frame after the other on one stream"},
+            "config": run_config(),
             "forward_builds_ms": {"inference (value; torch.no_grad(): no final_T / n_contrib / first-emission writes)": round(ms_per_step, 4),
                                   "tracking (what a training iteration runs)": None if track_ms is None else round(track_ms, 4)},
             "train_iters_per_s": None if train_ips is None else round(train_ips, 3),

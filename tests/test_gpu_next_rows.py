@@ -269,7 +269,7 @@ def test_distcuda2_large_cloud_and_init_scales():
 
 
 @pytest.mark.parametrize("mode,nproc", [("C", 2), ("C", 3), ("B", 2), ("A", 2), ("C-fixed", 2), ("C-fixed", 3)])
-def test_bench_multi_rank_path_on_one_gpu(mode, nproc):
+def test_bench_multi_rank_path_on_one_gpu(mode, nproc, tmp_path):
     """bench.py's N > 1 code path end to end -- first-contact probe of the collectives, band plan, mode C (Gaussian shards,
     route kernels, variable-size all-to-all of packed records forward and of gradient rows backward, pipelined frames) or
     mode B, strip all-gather, max-over-ranks timing -- with the ranks sharing this box's single GPU over gloo.  RCCL itself
@@ -285,9 +285,10 @@ def test_bench_multi_rank_path_on_one_gpu(mode, nproc):
         port = sk.getsockname()[1]
     env = dict(os.environ, GSR_BENCH_SHARED_GPU="1", GSR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc),
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--full",
            "--steps", "3", "--warmup", "1", "--P", "60000", "--width", "640", "--height", "368", "--no-cpu-baseline",
            "--min-warm-seconds", "0.2", "--mode", mode.split("-")[0]]
+    cmd += ["--dump-outputs", str(tmp_path / "outputs")]      # rank 0's assembled image of the last timed frame
     fixed = mode.endswith("-fixed")      # the fixed-capacity form of mode C's exchange (no count matrix on the host)
     if fixed:
         cmd += ["--exchange", "fixed"]
@@ -305,6 +306,20 @@ def test_bench_multi_rank_path_on_one_gpu(mode, nproc):
     if fixed:
         ex = d["config"]["exchange"]
         assert ex["form"] == "fixed" and ex["capacity"] > 0 and ex["frames_fixed"] > ex["frames_exact"] >= 1, ex
+    # the dumped image is the whole frame: the single-GPU operator's image of the same seeded scene
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_gaussians
+    P, W, H = 60000, 640, 368
+    got = np.load(tmp_path / "outputs" / "color.npy")
+    assert got.dtype == np.float32 and got.shape == (3, H, W) and sorted(os.listdir(tmp_path / "outputs")) == ["color.npy"]
+    dev = torch.device("cuda:0")
+    cam = make_camera(W, H)
+    sc = make_scene(P, cam, seed=0, s_med=0.012).to(dev)
+    camd = cam.to(dev)
+    rs = GaussianRasterizationSettings(H, W, cam.tanfovx, cam.tanfovy, torch.zeros(3, device=dev), 1.0, camd.world_view_transform,
+                                       camd.full_proj_transform, 3, camd.camera_center, False, False, False)
+    with torch.no_grad():
+        color = rasterize_gaussians(sc.means3D, None, sc.shs, None, sc.opacities, sc.scales, sc.rotations, None, rs, None)[0]
+    assert np.abs(got - color.cpu().numpy()).max() <= 1e-5
 
 
 def test_bench_reports_an_error_line_instead_of_dying_silently():
@@ -321,6 +336,44 @@ def test_bench_reports_an_error_line_instead_of_dying_silently():
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and "no_such_option" in json.loads(lines[0])["error"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline line only; the frames rendered between the two synchronisations that bound its
+    timed region (counted by bench.py's frame counter, not echoed from the argument) are exactly --steps; --dump-outputs writes
+    what the last timed frame returned -- the same arrays, bit for bit, as the operator gives a caller for the same seeded frame."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from helpers import ROOT
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, rasterize_gaussians
+    P, W, H = 20000, 320, 192
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--P", str(P),
+                        "--width", str(W), "--height", str(H), "--min-warm-seconds", "0.2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=200, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["timed_frames"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mpix/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and abs(d["value"] - W * H / (d["ms_per_step"] * 1e3)) <= 3e-3 * d["value"]
+    assert "train_iters_per_s" not in d and "stage_ms" not in d and "cpu_baseline" not in d      # (the context legs run with --full)
+    got = {n: np.load(out / f"{n}.npy") for n in ("color", "radii", "invdepth")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["color"].shape == (3, H, W) and got["invdepth"].shape == (1, H, W) and got["radii"].shape == (P,)
+    dev = torch.device("cuda:0")
+    cam = make_camera(W, H)
+    sc = make_scene(P, cam, seed=0, s_med=0.012).to(dev)
+    camd = cam.to(dev)
+    rs = GaussianRasterizationSettings(H, W, cam.tanfovx, cam.tanfovy, torch.zeros(3, device=dev), 1.0, camd.world_view_transform,
+                                       camd.full_proj_transform, 3, camd.camera_center, False, False, False)
+    with torch.no_grad():
+        color, radii, invd = rasterize_gaussians(sc.means3D, None, sc.shs, None, sc.opacities, sc.scales, sc.rotations, None, rs, None)
+    assert np.array_equal(got["color"], color.cpu().numpy()) and np.array_equal(got["invdepth"], invd.cpu().numpy())
+    assert np.array_equal(got["radii"], radii.cpu().numpy().astype(np.float32))
+    assert d["config"]["visible"] == int((radii > 0).sum()) > 0
 
 
 def test_view_sequence_with_changing_instance_counts():

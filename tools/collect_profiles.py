@@ -1,6 +1,6 @@
-"""Turn the output of tools/gpu_profile.sh (gpurun_out/p_bench_default.log, prof_stats/, prof_fetch/, prof_write/) into the
+"""Turn the output of tools/gpu_profile.sh ($OUT/p_bench_default.log, prof_stats/, prof_fetch/, prof_write/) into the
 committed summaries under profiles/:
-    rNN_bench_default.json        the default `python bench.py` JSON line
+    rNN_bench_default.json        the `python bench.py --full` JSON line
     rNN_kernel_stats.csv          rocprofv3 --kernel-trace --stats per-kernel table
     rNN_pmc_per_kernel.csv        FETCH_SIZE / WRITE_SIZE per kernel and launch (separate passes)
     pmc_latest.json               the same, keyed by kernel name -- bench.py reads roofline.traffic from here
@@ -14,10 +14,10 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("OUT") or os.path.join(ROOT, "out")      # the folder tools/gpu_profile.sh wrote to
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-# where the summaries go: profiles/ (run locally on merged-back raw files) or, on the GPU box, a directory under gpurun_out/ -- the raw
-# counter files of five rocprofv3 passes exceed what gpurun merges back (64 MiB), so tools/gpu_profile.sh summarises there and deletes them
+# where the summaries go: profiles/ (run locally on copied-back raw files) or, on the GPU machine, a directory under $OUT -- the raw
+# counter files of five rocprofv3 passes are too large to copy back, so tools/gpu_profile.sh summarises there and deletes them
 OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
 os.makedirs(OUT, exist_ok=True)
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Copies what a round's GPU calls left under gpurun_out/ (scratch) into profiles/ (tracked) under the round's names:
     python tools/collect_round_outputs.py r06
-Only files that exist are copied; prints what it did.  (tools/collect_profiles.py makes gpurun_out/profiles_<tag>/ ON the box; this runs in the repo.)"""
+Only files that exist are copied; prints what it did.  (tools/collect_profiles.py makes $OUT/profiles_<tag>/ on the GPU machine; this runs in the repo.)"""
 import glob
 import json
 import os
@@ -11,7 +11,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r06"
 G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
-pairs = [(f, os.path.join(P, os.path.basename(f))) for f in glob.glob(os.path.join(G, f"profiles_{tag}", "*"))]
+A = os.environ.get("OUT") or os.path.join(ROOT, "out")      # where the tools/gpu_*.sh scripts with an OUT folder wrote
+pairs = [(f, os.path.join(P, os.path.basename(f))) for f in glob.glob(os.path.join(A, f"profiles_{tag}", "*"))]
 for src, dst in (("train_run_sparse.json", "train_run_sparse"), ("train_run_sparse_growth.json", "train_run_sparse_growth"), ("train_run_sparse_fused_sh.json", "train_run_sparse_fused_sh"),
                  ("shard_model.json", "shard_model"), ("train_run_sparse_timeline_grown.json", "train_timeline_grown"), ("train_kernel_timeline_grown.json", "train_kernel_timeline_grown"),
                  ("depth_distribution_probe.json", "depth_distribution_probe"), ("parity_report.json", "parity_report"), ("host_cprofile.json", "host_cprofile"),
@@ -26,9 +27,9 @@ for src, dst in (("train_run_sparse.json", "train_run_sparse"), ("train_run_spar
 for s, d in pairs:
     shutil.copyfile(s, d)
     print(f"{os.path.relpath(s, ROOT)} -> {os.path.relpath(d, ROOT)}")
-# library A/B (tools/gpu_ab.sh LIBS=...): ab_<lib>_<rep>.log -> one json
+# library A/B (tools/gpu_ab.sh LIBS=...): ab_<lib>_<rep>.log in the folder gpu_ab.sh wrote to ($OUT, default out/) -> one json
 ab = {}
-for f in sorted(glob.glob(os.path.join(G, "ab_lib*_[0-9].log"))):
+for f in sorted(glob.glob(os.path.join(A, "ab_lib*_[0-9].log"))):
     lib = os.path.basename(f)[3:-6]
     try:
         d = json.loads([ln for ln in open(f) if ln.startswith("{")][-1])

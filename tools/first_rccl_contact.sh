@@ -30,7 +30,7 @@ for n in 1 2 4 8; do
   [ "$n" -le "$NMAX" ] || continue
   for cfg in "--mode C --exchange exact" "--mode C --exchange fixed" "--mode A"; do
     [ "$n" -eq 1 ] && [ "$cfg" != "--mode C --exchange exact" ] && continue
-    if [ "$n" -eq 1 ]; then CMD="python bench.py"; else CMD="python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29520 + n)) bench.py"; fi
+    if [ "$n" -eq 1 ]; then CMD="python bench.py --full"; else CMD="python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29520 + n)) bench.py --full"; fi
     GSR_BENCH_TIMEOUT_S=180 timeout 900 $CMD --gpus $n --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-full-loop --densify-iters 0 $cfg > gpurun_out/rccl_n${n}.log 2>&1
     L=$(grep '^{' gpurun_out/rccl_n${n}.log | tail -1)
     if [ -n "$L" ]; then echo "$L" >> gpurun_out/rccl_scale.jsonl; else echo "N=$n $cfg: no bench line"; tail -5 gpurun_out/rccl_n${n}.log; fi

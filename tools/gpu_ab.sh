@@ -6,13 +6,14 @@
 #   LIBS="lib lib_prev" bash tools/gpu_ab.sh          compares LIBRARIES instead (tools/build_prev_lib.sh builds lib_prev from
 #                                                       an earlier revision); three interleaved runs each
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
-mkdir -p gpurun_out
+OUT="${OUT:-out}"      # where the logs go
+mkdir -p "$OUT" && OUT="$(cd "$OUT" && pwd)"
 export TMPDIR=/tmp
 if [ -n "$LIBS" ]; then
   for rep in 1 2 3; do
     for lib in $LIBS; do
-      GSR_LIB="$PWD/gaussian-splatting_amd/$lib/libgsr_hip.so" timeout 300 python bench.py --no-other-configs --no-cpu-baseline --no-in-flight --no-pmc --densify-iters 0 > gpurun_out/ab_${lib}_$rep.log 2>&1
-      python - "$lib" "$rep" "gpurun_out/ab_${lib}_$rep.log" <<'PY'
+      GSR_LIB="$PWD/gaussian-splatting_amd/$lib/libgsr_hip.so" timeout 300 python bench.py --full --no-other-configs --no-cpu-baseline --no-in-flight --no-pmc --densify-iters 0 > $OUT/ab_${lib}_$rep.log 2>&1
+      python - "$lib" "$rep" "$OUT/ab_${lib}_$rep.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[3]) if l.startswith("{")][-1])
 print(f"{sys.argv[1]} rep {sys.argv[2]}:", d["value"], d["ms_per_step"], d["train_iters_per_s"], d["stage_ms"])
@@ -27,8 +28,8 @@ for rep in 1 2; do
   for cfg in "$@"; do
     i=$((i+1))
     opts=""; for o in ${cfg//,/ }; do opts="$opts --opt $o"; done
-    timeout 300 python bench.py --no-other-configs --no-cpu-baseline --no-in-flight --no-pmc --densify-iters 0 $opts > gpurun_out/ab_${i}_$rep.log 2>&1
-    python - "$cfg" "$rep" "gpurun_out/ab_${i}_$rep.log" <<'PY'
+    timeout 300 python bench.py --full --no-other-configs --no-cpu-baseline --no-in-flight --no-pmc --densify-iters 0 $opts > $OUT/ab_${i}_$rep.log 2>&1
+    python - "$cfg" "$rep" "$OUT/ab_${i}_$rep.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[3]) if l.startswith("{")][-1])
 print(f"{sys.argv[1]} rep {sys.argv[2]}:", d["value"], d["ms_per_step"], d["train_iters_per_s"], d["stage_ms"])

@@ -4,6 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_EXTRA="--full $BENCH_EXTRA"      # (the train legs run with --full)
 R="$PWD"
 cd /tmp
 rm -rf "$R/gpurun_out/prof_k"
