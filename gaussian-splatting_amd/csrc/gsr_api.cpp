@@ -1047,12 +1047,13 @@ int gsr_backward_blend(const GsrRasterSettings* settings, int P, int32_t num_ren
     return GSR_OK;
 }
 
-int gsr_backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
-                            const float* colors_precomp, const float* opacities, const float* scales,
-                            const float* rotations, const float* cov3D_precomp, const int32_t* radii,
-                            const void* geom_buffer, const float* splat_grads, float* dL_dmeans2D, float* dL_dcolors,
-                            float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                            float* dL_drotations, void* stream) {
+// gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera
+static int backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                               const float* colors_precomp, const float* opacities, const float* scales,
+                               const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                               const void* geom_buffer, const float* splat_grads, float* dL_dmeans2D, float* dL_dcolors,
+                               float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                               float* dL_drotations, const GsrCameraGrads* camera, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GsrCamDev cam;
     int rc = make_cam(settings, M, cam);
@@ -1061,7 +1062,20 @@ int gsr_backward_preprocess(const GsrRasterSettings* settings, int P, int M, con
     if (rc != GSR_OK) return rc;
     rc = check_split_sh(settings, P, M, shs, true);
     if (rc != GSR_OK) return rc;
-    if (P == 0) return GSR_OK;
+    if (camera) {
+        if (!camera->dL_dviewmatrix || !camera->dL_dprojmatrix || !camera->dL_dcampos)
+            return fail(GSR_ERR_INVALID_ARG, "camera gradient outputs are NULL");
+        if (P > 0 && !camera->scratch) return fail(GSR_ERR_INVALID_ARG, "camera gradient scratch is NULL");
+        if (((uintptr_t)camera->scratch) & 7) return fail(GSR_ERR_INVALID_ARG, "camera gradient scratch must be 8-byte aligned");
+    }
+    if (P == 0) {
+        if (camera) {      // no Gaussian, no gradient
+            HIP_OK(hipMemsetAsync(camera->dL_dviewmatrix, 0, 16 * sizeof(float), st));
+            HIP_OK(hipMemsetAsync(camera->dL_dprojmatrix, 0, 16 * sizeof(float), st));
+            HIP_OK(hipMemsetAsync(camera->dL_dcampos, 0, 3 * sizeof(float), st));
+        }
+        return GSR_OK;
+    }
     (void)geom_buffer;      // the colour clamp bits are recomputed; a NULL geometry buffer is accepted (Gaussian-sharded backward)
     if (!radii || !splat_grads) return fail(GSR_ERR_INVALID_ARG, "radii / splat_grads are NULL");
     if (!dL_dmeans2D || !dL_dopacity || !dL_dmeans3D) return fail(GSR_ERR_INVALID_ARG, "gradient outputs are NULL");
@@ -1072,14 +1086,47 @@ int gsr_backward_preprocess(const GsrRasterSettings* settings, int P, int M, con
         return fail(GSR_ERR_UNSUPPORTED, "split SH form needs 16-byte aligned dL_dsh / dL_dsh_dc");
     if (scales && (!dL_dscales || !dL_drotations)) return fail(GSR_ERR_INVALID_ARG, "dL_dscales / dL_drotations are NULL");
     GsrGeom g = gsr_carve_geom(geom_buffer ? (char*)geom_buffer : nullptr, P);
+    GsrCamGradDev camg{};
+    if (camera) {
+        camg.partials = (double*)camera->scratch;
+        camg.dview = camera->dL_dviewmatrix;
+        camg.dproj = camera->dL_dprojmatrix;
+        camg.dcampos = camera->dL_dcampos;
+    }
     {   StageTimer t(GSR_STAGE_PREPROCESS_BWD, st);
         gsr_launch_preprocess_backward(cam, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                        radii, g, splat_grads, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
-                                       dL_dsh, scales ? dL_dscales : nullptr, scales ? dL_drotations : nullptr, st);
+                                       dL_dsh, scales ? dL_dscales : nullptr, scales ? dL_drotations : nullptr, st,
+                                       camera ? &camg : nullptr);
     }
     STAGE_CHECK("preprocess backward");
     HIP_OK(hipGetLastError());
     return GSR_OK;
+}
+
+int gsr_backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                            const float* colors_precomp, const float* opacities, const float* scales,
+                            const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                            const void* geom_buffer, const float* splat_grads, float* dL_dmeans2D, float* dL_dcolors,
+                            float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                            float* dL_drotations, void* stream) {
+    return backward_preprocess(settings, P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                               geom_buffer, splat_grads, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                               dL_dscales, dL_drotations, nullptr, stream);
+}
+
+size_t gsr_camera_grad_scratch_bytes(int P) { return gsr_camera_grad_rows(P) * 27 * sizeof(double); }
+
+int gsr_backward_preprocess_camera(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                                   const float* colors_precomp, const float* opacities, const float* scales,
+                                   const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                   const void* geom_buffer, const float* splat_grads, float* dL_dmeans2D, float* dL_dcolors,
+                                   float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                                   float* dL_drotations, const GsrCameraGrads* camera, void* stream) {
+    if (!camera) return fail(GSR_ERR_INVALID_ARG, "camera is NULL");
+    return backward_preprocess(settings, P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                               geom_buffer, splat_grads, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                               dL_dscales, dL_drotations, camera, stream);
 }
 
 int gsr_backward_preprocess_sh_adam(const GsrRasterSettings* settings, int P, int M, const float* means3D, float* shs_rest,

@@ -157,7 +157,18 @@ void gsr_launch_preprocess_backward(const GsrCamDev& cam, int P, const float* me
                                     const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                     GsrGeom g, const float* splat_grads /*[P,12]*/, float* dL_dmeans2D,
                                     float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D,
-                                    float* dL_dsh, float* dL_dscales, float* dL_drotations, hipStream_t st);
+                                    float* dL_dsh, float* dL_dscales, float* dL_drotations, hipStream_t st,
+                                    const struct GsrCamGradDev* camg = nullptr);
+// camera gradients (gsr_backward_preprocess_camera): with `camg` the launcher runs the kernel's CAM instantiation, which also writes
+// per-workgroup fp64 partial sums [27][grid] into `partials`, and a one-workgroup kernel that sums them into the three fp32 outputs
+struct GsrCamGradDev {
+    double* partials;      // gsr_camera_grad_rows(P) * 27 doubles
+    float* dview;          // [16]
+    float* dproj;          // [16]
+    float* dcampos;        // [3]
+};
+#define GSR_CAM_MAX_ROWS 1024
+size_t gsr_camera_grad_rows(int P);      // workgroups of the CAM launch at most: ceil(P / 256) capped at GSR_CAM_MAX_ROWS
 // the same kernel, but the SH gradient of the split form is not written: the Adam update of the two SH tensors is applied in
 // place from the gradient tile (gsr_backward_preprocess_sh_adam); dense: every row, sparse: rows with radii > 0
 struct GsrShAdamDev {

@@ -432,9 +432,20 @@ struct GsrSplatGrad {          // what the render backward accumulates per Gauss
 // tests/golden/hard_frames.npz) and a scale gradient 8e-4.  In fp64 from the SAME fp32 inputs and the same fp32 per-pair sums of
 // the blend backward the frame is at 6e-5.  The kernel streams 500+ bytes per Gaussian: the extra ALU time hides under the loads.
 // The two frustum-clamp decisions are taken on the fp32 quotients, exactly as the forward took them.
+// What the camera gradient (gsr_backward_preprocess_camera) needs of gsr_project_backward_r, in fp32 (one rounding per Gaussian and
+// term; the sums over the Gaussians are fp64): dt = dL/d(view-space position) after the frustum-clamp masks, the covariance path's
+// share of dL/dW through T = J W -- wcov[3 j + r] = dL/dW[r][j]: J00 dT0j, J11 dT1j, J02 dT0j + J12 dT1j -- and dh = dL/d(clip
+// position).  Each is stored as soon as it is known: the caller may point `terms` at LDS, so that nothing extra stays live in
+// registers through the chain.  With the default NULL the compiler drops every store, and the Gaussian gradients are the same bits.
+struct GsrProjTerms {
+    float dt[3];
+    float wcov[9];
+    float dh[3];
+};
 template <class R>
 GSR_HD void gsr_project_backward_r(const GsrCam& cam, const float* mean, const R* cov, float opacity_in,
-                                   const GsrSplatGrad& g, float* dmean, R* dcov, float& dopacity_in) {
+                                   const GsrSplatGrad& g, float* dmean, R* dcov, float& dopacity_in,
+                                   GsrProjTerms* terms = nullptr) {
     const float* vm = cam.view;
     const float* pm = cam.proj;
     const float x = mean[0], y = mean[1], z = mean[2];
@@ -519,6 +530,13 @@ GSR_HD void gsr_project_backward_r(const GsrCam& cam, const float* mean, const R
     // dL/dT: a = sum T0j u_j (u = S T0): da/dT0j = 2 u_j ; b = sum T1j u_j: db/dT1j = u_j, db/dT0j = v_j ; dc/dT1j = 2 v_j
     const R dT00 = two * u0 * da + v0 * db, dT01 = two * u1 * da + v1 * db, dT02 = two * u2 * da + v2 * db;
     const R dT10 = two * v0 * dc + u0 * db, dT11 = two * v1 * dc + u1 * db, dT12 = two * v2 * dc + u2 * db;
+    if (terms) {
+        terms->wcov[0] = (float)(J00 * dT00); terms->wcov[3] = (float)(J00 * dT01); terms->wcov[6] = (float)(J00 * dT02);
+        terms->wcov[1] = (float)(J11 * dT10); terms->wcov[4] = (float)(J11 * dT11); terms->wcov[7] = (float)(J11 * dT12);
+        terms->wcov[2] = (float)(J02 * dT00 + J12 * dT10);
+        terms->wcov[5] = (float)(J02 * dT01 + J12 * dT11);
+        terms->wcov[8] = (float)(J02 * dT02 + J12 * dT12);
+    }
     // T0j = J00 W0j + J02 W2j ; T1j = J11 W1j + J12 W2j
     const R dJ00 = W00 * dT00 + W01 * dT01 + W02 * dT02;
     const R dJ02 = W20 * dT00 + W21 * dT01 + W22 * dT02;
@@ -548,6 +566,10 @@ GSR_HD void gsr_project_backward_r(const GsrCam& cam, const float* mean, const R
     dmean[0] += (float)(W00 * dtx + W10 * dty + W20 * dtz);
     dmean[1] += (float)(W01 * dtx + W11 * dty + W21 * dtz);
     dmean[2] += (float)(W02 * dtx + W12 * dty + W22 * dtz);
+    if (terms) {
+        terms->dt[0] = (float)dtx; terms->dt[1] = (float)dty; terms->dt[2] = (float)dtz;
+        terms->dh[0] = dhx; terms->dh[1] = dhy; terms->dh[2] = dhw;
+    }
 }
 // the all-fp32 form (rounds 1-5; kept for the tests that hold it against the fp32 oracle's autograd operation by operation)
 GSR_HD void gsr_project_backward(const GsrCam& cam, const float* mean, const float* cov, float opacity_in,
@@ -576,7 +598,8 @@ GSR_HD void gsr_sh_bwd_term(GsrShBwdAcc& a, const float* s3, float* d3, float ba
 }
 template <class Row, class RowOut>
 GSR_HD void gsr_sh_backward_row(int deg, int M, const Row& sh, const float* mean, const float* campos,
-                                uint32_t clamped, const float* drgb_in, const RowOut& dsh, float* dmean) {
+                                uint32_t clamped, const float* drgb_in, const RowOut& dsh, float* dmean,
+                                float* ddir = nullptr) {
     const float ox = mean[0] - campos[0], oy = mean[1] - campos[1], oz = mean[2] - campos[2];
     const float n = sqrtf(ox * ox + oy * oy + oz * oz);
     const float x = ox / n, y = oy / n, z = oz / n;
@@ -629,9 +652,18 @@ GSR_HD void gsr_sh_backward_row(int deg, int M, const Row& sh, const float* mean
     // d = o / |o|  =>  dL/do = (dL/dd - d (d . dL/dd)) / |o|
     const float dd = x * a.ddx + y * a.ddy + z * a.ddz;
     const float inv = 1.0f / n;
-    dmean[0] += (a.ddx - x * dd) * inv;
-    dmean[1] += (a.ddy - y * dd) * inv;
-    dmean[2] += (a.ddz - z * dd) * inv;
+    if (ddir) {      // the same roundings -- each term is formed, then added -- with the term kept: dL/dcampos = -ddir
+        ddir[0] = (a.ddx - x * dd) * inv;
+        ddir[1] = (a.ddy - y * dd) * inv;
+        ddir[2] = (a.ddz - z * dd) * inv;
+        dmean[0] += ddir[0];
+        dmean[1] += ddir[1];
+        dmean[2] += ddir[2];
+    } else {
+        dmean[0] += (a.ddx - x * dd) * inv;
+        dmean[1] += (a.ddy - y * dd) * inv;
+        dmean[2] += (a.ddz - z * dd) * inv;
+    }
 }
 GSR_HD void gsr_sh_backward(int deg, int M, const float* sh, const float* mean, const float* campos,
                             uint32_t clamped, const float* drgb_in, float* dsh, float* dmean) {

@@ -401,8 +401,45 @@ __device__ __forceinline__ void wave_adam_sh_split_dense(const GsrShAdamDev& ad,
     __builtin_amdgcn_wave_barrier();
 }
 
+// ---- camera gradients (gsr_backward_preprocess_camera) ----
+// GSR_CAM_TERMS sums over the visible Gaussians: dL/dV rows 0-2 (12), dL/dP rows 0, 1, 3 (12), the SH view-direction term (3).
+// Term c < 12: view element (row c % 3, col c / 3); 12 <= c < 24: projection row {0, 1, 3}[(c - 12) % 3], col (c - 12) / 3; then 3 x campos.
+constexpr int GSR_CAM_TERMS = 27;
+// a double through a 32-bit lane exchange, as two halves (the only width every wave primitive -- and tests/simt -- moves)
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+    uint64_t u;
+    __builtin_memcpy(&u, &v, 8);
+    const uint32_t lo = __shfl_xor((uint32_t)u, m), hi = __shfl_xor((uint32_t)(u >> 32), m);
+    u = ((uint64_t)hi << 32) | lo;
+    __builtin_memcpy(&v, &u, 8);
+    return v;
+}
+// The wave's 64 rows of 16 fp32 terms (row = lane, stride CAM_ROW) summed column by column in fp64: lane L returns the sum of column
+// L & 15 -- its quarter L >> 4 of the rows in row order, then the four quarters pairwise.  The order of the additions is fixed by the
+// lane numbers alone and the four lanes of a column add the same operands: the same bits on every run and on all four lanes.
+constexpr int CAM_ROW = 17;      // floats per row (odd: the column reads of a quarter spread over the banks)
+__device__ __forceinline__ double wave_column_sum16(const float* t, int lane) {
+    __builtin_amdgcn_wave_barrier();      // every lane's row is written
+    const int c = lane & 15, r0 = (lane >> 4) * 16;
+    double s = (double)t[r0 * CAM_ROW + c];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) s = s + (double)t[(r0 + k) * CAM_ROW + c];
+    __builtin_amdgcn_wave_barrier();      // ... and read before the rows are written again
+    s = s + shfl_xor_f64(s, 16);
+    return s + shfl_xor_f64(s, 32);
+}
+// the kernel's last argument: the Adam block (ADAM; an unused, empty one otherwise -- the argument list of the instantiations without
+// camera gradients is the one they always had) or, with CAM, the partial sums [GSR_CAM_TERMS][gridDim.x] the workgroups write
+struct GsrCamPartialsDev {
+    double* partials;
+};
+template <bool CAM> struct GsrBwdTail { typedef GsrShAdamDev type; };
+template <> struct GsrBwdTail<true> { typedef GsrCamPartialsDev type; };
+
 // `shs` carries no __restrict__: in the ADAM instantiation it is adam.rest, which the kernel also writes (the update in place)
-template <bool SPLIT, bool ADAM = false>
+// CAM (never with ADAM): also the camera gradient's partial sums, reduced per wave iteration (lane L keeps column L & 15 in fp64), combined
+// over the four waves through LDS after the grid-stride loop and written as one column entry per workgroup; camera_grad_finish_kernel sums them.
+template <bool SPLIT, bool ADAM = false, bool CAM = false>
 __global__ void __launch_bounds__(256) GSR_PRE_OCC_BWD
 preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, const float* shs,
                       const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -411,8 +448,11 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
                       const uint32_t* __restrict__ clamped, const float4* __restrict__ grads,
                       float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity,
                       float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
-                      float* __restrict__ dL_dscales, float* __restrict__ dL_drotations, GsrShAdamDev adam) {
+                      float* __restrict__ dL_dscales, float* __restrict__ dL_drotations, typename GsrBwdTail<CAM>::type adam) {
+    static_assert(!(ADAM && CAM), "the fused SH Adam step and the camera gradient are not combined");
     __shared__ __attribute__((aligned(16))) float s_sh[4][64 * SH_ROW];
+    // CAM: the wave's rows of camera terms (17 KB; with the SH tiles 70 KB per workgroup: two workgroups per CU as before)
+    __shared__ float s_cam[CAM ? 4 : 1][CAM ? 64 * CAM_ROW : 1];
     GsrCam cam;
     load_cam(camd, cam);
     const int M = cam.M;
@@ -422,9 +462,12 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
     float* dL_ddc = SPLIT ? camd.dL_dsh_dc : nullptr;
     const bool staged_sh = shs != nullptr && M == 16;
     constexpr int sh_row = SH_ROW;
+    // CAM: this lane's running sums of view column lane & 15 (0..11; 12..14: the SH term) and projection column lane & 15
+    double cam_acc_v = 0.0, cam_acc_p = 0.0;
     for (int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane; i0 < P; i0 += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = i0 + lane;
         const bool in_range = i < P;
+        [[maybe_unused]] float ddir[3] = {0.f, 0.f, 0.f};      // CAM: the SH backward's view-direction term
         float dmean[3] = {0.f, 0.f, 0.f};
         float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (what is stored; the chain itself runs in GsrBwdReal, gsr_math.h)
         float dscale[3] = {0.f, 0.f, 0.f};
@@ -470,7 +513,12 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
 #pragma unroll
                 for (int k = 0; k < 6; ++k) covr[k] = cov[k];
             }
-            gsr_project_backward_r<GsrBwdReal>(cam, mean, covr, op_in, g, dmean, dcovr, dop);
+            if constexpr (CAM) {      // the terms go straight to the lane's LDS row (15 floats of CAM_ROW)
+                gsr_project_backward_r<GsrBwdReal>(cam, mean, covr, op_in, g, dmean, dcovr, dop,
+                                                   reinterpret_cast<GsrProjTerms*>(s_cam[wv] + lane * CAM_ROW));
+            } else {
+                gsr_project_backward_r<GsrBwdReal>(cam, mean, covr, op_in, g, dmean, dcovr, dop);
+            }
             // the returned means2D gradient is in NDC-scaled units (SURVEY A.5 units trap)
             dm2x = g.dpx * (0.5f * (float)cam.W);
             dm2y = g.dpy * (0.5f * (float)cam.H);
@@ -490,17 +538,17 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
                         const GsrShRowSplit row{tile + SPLIT_DC + lane * 3, tile + lane * 45};
                         gsr_sh_to_rgb_row(cam.sh_degree, 16, row, mean, cam.campos, rgb_unused, clampbits);
                         gsr_sh_backward_row(cam.sh_degree, 16, row, mean, cam.campos, clampbits, drgb,
-                                            GsrShRowSplitOut{tile + SPLIT_DC + lane * 3, tile + lane * 45}, dmean);
+                                            GsrShRowSplitOut{tile + SPLIT_DC + lane * 3, tile + lane * 45}, dmean, CAM ? ddir : nullptr);
                     } else {
                         const GsrShRowAligned row{tile + lane * sh_row};
                         gsr_sh_to_rgb_row(cam.sh_degree, 16, row, mean, cam.campos, rgb_unused, clampbits);
                         gsr_sh_backward_row(cam.sh_degree, 16, row, mean, cam.campos, clampbits, drgb,
-                                            GsrShRowAlignedOut{tile + lane * sh_row}, dmean);
+                                            GsrShRowAlignedOut{tile + lane * sh_row}, dmean, CAM ? ddir : nullptr);
                     }
                 } else if (!SPLIT) {
                     gsr_sh_to_rgb(cam.sh_degree, M, shs + i * (int64_t)M * 3, mean, cam.campos, rgb_unused, clampbits);
-                    gsr_sh_backward(cam.sh_degree, M, shs + i * (int64_t)M * 3, mean, cam.campos, clampbits, drgb,
-                                    dL_dsh + i * (int64_t)M * 3, dmean);
+                    gsr_sh_backward_row(cam.sh_degree, M, GsrShRow{shs + i * (int64_t)M * 3}, mean, cam.campos, clampbits, drgb,
+                                        GsrShRowOut{dL_dsh + i * (int64_t)M * 3}, dmean, CAM ? ddir : nullptr);
                 }
             }
         } else if (shs) {
@@ -525,9 +573,40 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
             }
         }
         if (staged_sh) {
-            if (SPLIT && ADAM) wave_adam_sh_split_dense(adam, i0, P, adam.sparse ? __ballot(vis) : ~0ull, lane, tile);
+            if constexpr (SPLIT && ADAM) wave_adam_sh_split_dense(adam, i0, P, adam.sparse ? __ballot(vis) : ~0ull, lane, tile);
             else if (SPLIT) wave_store_sh_split_dense(dL_ddc, dL_dsh, i0, P, lane, tile);
             else wave_store_sh16(dL_dsh, i0, P, lane, tile);
+        }
+        if constexpr (CAM) {      // (wave-uniform: every lane of the wave is here)
+            // Row layout of GsrProjTerms: dt[3], wcov[9], dh[3].  Rewritten in place into the 16 columns of the view pass -- column
+            // 3 j + r = dL/dV[r][j] = dt_r p_j + wcov[3 j + r] (p = (x, y, z, 1)), then the SH term -- and then of the projection pass:
+            // dL/dP[row][j] = dh_row p_j, row {0, 1, 3}[r].  A lane that is not visible wrote nothing: its terms are zero.
+            float* rowp = s_cam[wv] + lane * CAM_ROW;
+            float dtf[3], dhf[3], w[9];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) { dtf[r] = vis ? rowp[r] : 0.f; dhf[r] = vis ? rowp[12 + r] : 0.f; }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w[k] = vis ? rowp[3 + k] : 0.f;
+            const double p[3] = {(double)mean[0], (double)mean[1], (double)mean[2]};
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) rowp[3 * j + r] = (float)((double)dtf[r] * p[j] + (double)w[3 * j + r]);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                rowp[9 + r] = dtf[r];
+                rowp[12 + r] = ddir[r];
+            }
+            rowp[15] = 0.f;
+            cam_acc_v += wave_column_sum16(s_cam[wv], lane);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) rowp[3 * j + r] = (float)((double)dhf[r] * p[j]);
+                rowp[9 + r] = dhf[r];
+            }
+            rowp[12] = rowp[13] = rowp[14] = 0.f;
+            cam_acc_p += wave_column_sum16(s_cam[wv], lane);
         }
         if (!in_range) continue;
         dL_dmeans2D[i * 3 + 0] = dm2x; dL_dmeans2D[i * 3 + 1] = dm2y; dL_dmeans2D[i * 3 + 2] = 0.f;
@@ -541,6 +620,59 @@ preprocess_bwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
             dL_dscales[i * 3 + 0] = dscale[0]; dL_dscales[i * 3 + 1] = dscale[1]; dL_dscales[i * 3 + 2] = dscale[2];
             reinterpret_cast<float4*>(dL_drotations)[i] = make_float4(drot[0], drot[1], drot[2], drot[3]);
         }
+    }
+    if constexpr (CAM) {      // the four waves' sums, in wave order, through the (now free) SH tiles
+        __syncthreads();
+        double* red = reinterpret_cast<double*>(&s_sh[0][0]);
+        const int c = lane;      // partial term order: view 0..11, projection 12..23, campos 24..26
+        if (c < 15) red[wv * 32 + (c < 12 ? c : c + 12)] = cam_acc_v;
+        if (c < 12) red[wv * 32 + 12 + c] = cam_acc_p;
+        __syncthreads();
+        const int t = threadIdx.x;
+        if (t < GSR_CAM_TERMS) adam.partials[(int64_t)t * gridDim.x + blockIdx.x] = ((red[t] + red[32 + t]) + red[64 + t]) + red[96 + t];
+    }
+}
+
+// One workgroup: term c of the camera gradient = sum of partials[c][0 .. rows) in a fixed order (thread k sums rows k, k + 256, k + 512, k + 768;
+// then one thread per term adds the 256 thread sums in thread order), written in the caller's layout -- flat index i + 4 j is math
+// element (row i, col j) -- with the eight structural zeros (view row 3, projection row 2: no kernel reads them).
+__global__ void __launch_bounds__(256)
+camera_grad_finish_kernel(const double* __restrict__ partials, int rows, float* __restrict__ dview, float* __restrict__ dproj,
+                          float* __restrict__ dcampos) {
+    __shared__ double red[GSR_CAM_TERMS][257];
+    const int t = threadIdx.x;
+    static_assert(GSR_CAM_MAX_ROWS <= 4 * 256, "camera_grad_finish_kernel sums at most four rows per thread");
+    // rows <= GSR_CAM_MAX_ROWS = 4 x 256: four rows per thread, loaded branch-free (a row past the end reads row 0 and counts 0) so that the
+    // loads of all terms are in flight together
+#pragma unroll
+    for (int c = 0; c < GSR_CAM_TERMS; ++c) {
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = t + 256 * k;
+            v[k] = partials[(int64_t)c * rows + (r < rows ? r : 0)];
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s = s + (t + 256 * k < rows ? v[k] : 0.0);
+        red[c][t] = s;
+    }
+    __syncthreads();
+    if (t < GSR_CAM_TERMS) {
+        double s = 0.0;
+        for (int k = 0; k < 256; ++k) s += red[t][k];
+        if (t < 12) {
+            dview[t % 3 + 4 * (t / 3)] = (float)s;
+        } else if (t < 24) {
+            const int c = t - 12, row = c % 3 == 2 ? 3 : c % 3;
+            dproj[row + 4 * (c / 3)] = (float)s;
+        } else {
+            dcampos[t - 24] = (float)(-s);
+        }
+    }
+    if (t < 4) {
+        dview[3 + 4 * t] = 0.f;
+        dproj[2 + 4 * t] = 0.f;
     }
 }
 
@@ -585,15 +717,35 @@ void gsr_launch_preprocess_backward(const GsrCamDev& cam, int P, const float* me
                                     const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                     GsrGeom g, const float* splat_grads, float* dL_dmeans2D, float* dL_dcolors,
                                     float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                    float* dL_dscales, float* dL_drotations, hipStream_t st) {
+                                    float* dL_dscales, float* dL_drotations, hipStream_t st, const GsrCamGradDev* camg) {
 #define GSR_PRE_BWD(SPLIT_)                                                                                                     \
     hipLaunchKernelGGL((preprocess_bwd_kernel<SPLIT_>), dim3(stream_grid(P)), dim3(256), 0, st, cam, P, means3D, shs,             \
                        colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g.clamped,                                 \
                        reinterpret_cast<const float4*>(splat_grads), dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,     \
                        dL_dsh, dL_dscales, dL_drotations, GsrShAdamDev{})
+#define GSR_PRE_BWD_CAM(SPLIT_)                                                                                                 \
+    hipLaunchKernelGGL((preprocess_bwd_kernel<SPLIT_, false, true>), dim3(grid), dim3(256), 0, st, cam, P, means3D, shs,          \
+                       colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g.clamped,                                 \
+                       reinterpret_cast<const float4*>(splat_grads), dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,     \
+                       dL_dsh, dL_dscales, dL_drotations, GsrCamPartialsDev{camg->partials})
+    if (camg) {
+        // (at most gsr_camera_grad_rows(P) workgroups, whatever preprocess_grid_cap says: the scratch was sized by that)
+        const int grid = stream_grid(P) < (int)gsr_camera_grad_rows(P) ? stream_grid(P) : (int)gsr_camera_grad_rows(P);
+        if (cam.sh_dc) GSR_PRE_BWD_CAM(true);
+        else GSR_PRE_BWD_CAM(false);
+        hipLaunchKernelGGL(camera_grad_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)camg->partials, grid, camg->dview,
+                           camg->dproj, camg->dcampos);
+        return;
+    }
     if (cam.sh_dc) GSR_PRE_BWD(true);
     else GSR_PRE_BWD(false);
 #undef GSR_PRE_BWD
+#undef GSR_PRE_BWD_CAM
+}
+
+size_t gsr_camera_grad_rows(int P) {
+    const int64_t b = ((int64_t)(P > 0 ? P : 0) + 255) / 256;
+    return (size_t)(b < 1 ? 1 : (b > GSR_CAM_MAX_ROWS ? GSR_CAM_MAX_ROWS : b));
 }
 
 void gsr_launch_preprocess_backward_sh_adam(const GsrCamDev& cam, int P, const float* means3D, const float* opacities,

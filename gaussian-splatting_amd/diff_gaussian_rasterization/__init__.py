@@ -230,7 +230,9 @@ def fuse_sh_adam_into_backward(optimizer, dc_param, rest_param):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, tile_rows, grad_sync, dc):
+                raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None):
+        # viewmatrix / projmatrix / campos: raster_settings' own tensors, passed again so that autograd sees them (camera gradients,
+        # gsr_backward_preprocess_camera).  The kernels read them from raster_settings.
         lib = _lib.load()
         _require_cuda(means3D, "means3D")
         _trim_cache_if_pending()
@@ -260,7 +262,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         keep: list = []
         with torch.cuda.device(device):
             # inside autograd.Function.forward grad mode is off; needs_input_grad tells whether a backward can follow
-            no_backward = not (any(ctx.needs_input_grad[:8]) or ctx.needs_input_grad[11])
+            ctx.camera_grad = any(ctx.needs_input_grad[12:15])
+            no_backward = not (any(ctx.needs_input_grad[:8]) or ctx.needs_input_grad[11] or ctx.camera_grad)
             s = _make_settings(raster_settings, keep, tile_rows, no_backward)
             if dc_c is not None:
                 s.sh_dc = dc_c.data_ptr()
@@ -304,6 +307,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             ent = _SH_ADAM.get(id(sh))
             if ent is not None and ent.matches(dc, sh) and sh_c is sh and dc_c is dc and sh.requires_grad and dc.requires_grad:
                 ctx.sh_adam = ent
+        if ctx.sh_adam is not None and ctx.camera_grad:
+            raise GsrError("camera gradients (viewmatrix / projmatrix / campos requiring grad) cannot be combined with the SH Adam step "
+                           "fused into the backward (fuse_sh_adam_into_backward): remove the fusion or detach the camera tensors")
+        ctx.cam_meta = tuple((t.shape, t.dtype) if t is not None else None for t in (viewmatrix, projmatrix, campos))
         ctx.sh_given = sh is not None
         ctx.dc_shape = tuple(dc.shape) if dc is not None else None
         ctx.save_for_backward(means3D_c, sh_c if sh_c is not None else means3D_c.new_empty(0),
@@ -344,6 +351,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         dL_ddc = torch.empty(P, 1, 3, **f) if (has_dc and fused_adam is None) else None
         dL_dscales = torch.empty(P, 3, **f) if has_sc else None
         dL_drot = torch.empty(P, 4, **f) if has_rot else None
+        cam_out = cam_scratch = None
+        if ctx.camera_grad:      # [16] view, [16] projection, [3] campos (64-byte offsets), fp32
+            cam_out = torch.zeros(48, **f)
+            cam_scratch = torch.empty(max(int(lib.gsr_camera_grad_scratch_bytes(P)), 8), dtype=torch.uint8, device=device)
         if P > 0:
             g_color = _f32c(grad_out_color)
             g_depth = _f32c(grad_out_depth) if grad_out_depth is not None else None
@@ -375,6 +386,20 @@ class _RasterizeGaussians(torch.autograd.Function):
                             _ptr(rot) if has_rot else None, _ptr(cov) if has_cov else None, _ptr(radii), _ptr(geom), rec_ptr,
                             _ptr(dL_dmeans2D), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dscales),
                             _ptr(dL_drot), C.byref(adam), st), "gsr_backward_preprocess_sh_adam")
+                        return
+                    if ctx.camera_grad:
+                        # blend backward, (multi-GPU: record sum), then the per-Gaussian backward that also sums the camera gradient
+                        rec_ptr = C.c_void_p(0)
+                        _lib.check(lib.gsr_backward_blend(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img),
+                                                          _ptr(g_color), _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), st),
+                                   "gsr_backward_blend")
+                        if ctx.grad_sync is not None:
+                            off = int(rec_ptr.value) - scratch.data_ptr()
+                            ctx.grad_sync(scratch[off:off + P * 48].view(torch.float32).view(P, 12))
+                        camg = _lib.CameraGrads(cam_out.data_ptr(), cam_out.data_ptr() + 64, cam_out.data_ptr() + 128,
+                                                cam_scratch.data_ptr())
+                        _lib.check(lib.gsr_backward_preprocess_camera(C.byref(s), P, M, *inputs, _ptr(geom), rec_ptr, *outs,
+                                                                      C.byref(camg), st), "gsr_backward_preprocess_camera")
                         return
                     if ctx.grad_sync is None:
                         _lib.check(lib.gsr_rasterize_backward(C.byref(s), P, M, ctx.num_rendered, *inputs, _ptr(geom),
@@ -412,8 +437,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             dL_dsh = dL_dsh[:, 1:]
         elif has_dc and dL_ddc is not None:
             dL_ddc = dL_ddc.view(ctx.dc_shape)
+        cam_grads = (None, None, None)
+        if ctx.camera_grad:
+            cam_grads = tuple(None if (meta is None or not ctx.needs_input_grad[12 + k]) else
+                              cam_out[16 * k:16 * k + (3 if k == 2 else 16)].reshape(meta[0]).to(meta[1])
+                              for k, meta in enumerate(ctx.cam_meta))
         return (dL_dmeans3D, dL_dmeans2D if ctx.has_means2D else None, dL_dsh, dL_dcolors if has_col else None, dL_dopacity, dL_dscales, dL_drot,
-                dL_dcov3D if has_cov else None, None, None, None, dL_ddc)
+                dL_dcov3D if has_cov else None, None, None, None, dL_ddc) + cam_grads
 
 
 def _cpu_copy(args):
@@ -426,9 +456,12 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     per-Gaussian backward (multi-GPU: all-reduce of the 48-byte gradient records, parallel.py).
     `tile_rows=(y0, y1)` (extension) restricts binning + blending to that
     band of 16-pixel tile rows; pixels outside the band come back as zeros.  `dc` (the reference's separate_sh
-    form): SH coefficient 0 as [P,1,3]; `sh` then holds coefficients 1.. as [P,M-1,3]."""
+    form): SH coefficient 0 as [P,1,3]; `sh` then holds coefficients 1.. as [P,M-1,3].
+    Camera gradients (no reference counterpart): when raster_settings.viewmatrix / projmatrix / campos require grad, backward
+    returns their gradients too (include/gsr.h gsr_backward_preprocess_camera; with `tile_rows`, the band's contribution)."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, tile_rows, grad_sync, dc)
+                                     cov3Ds_precomp, raster_settings, tile_rows, grad_sync, dc, raster_settings.viewmatrix,
+                                     raster_settings.projmatrix, raster_settings.campos)
 
 
 class GaussianRasterizer(nn.Module):

@@ -45,6 +45,7 @@ EXPORTS = [
     "gsr_abi_version", "gsr_last_error", "gsr_geometry_bytes", "gsr_binning_bytes", "gsr_image_bytes",
     "gsr_backward_scratch_bytes",
     "gsr_rasterize_forward", "gsr_rasterize_backward", "gsr_backward_blend", "gsr_backward_preprocess",
+    "gsr_camera_grad_scratch_bytes", "gsr_backward_preprocess_camera",
     "gsr_preprocess_forward", "gsr_rasterize_from_splats",
     "gsr_route_scratch_bytes", "gsr_route_count", "gsr_route_pack", "gsr_rasterize_from_packed", "gsr_route_return",
     "gsr_route_pack_fixed", "gsr_rasterize_from_segments",
@@ -71,6 +72,11 @@ class ShAdam(C.Structure):
     _fields_ = [("dc_exp_avg", C.c_void_p), ("dc_exp_avg_sq", C.c_void_p), ("rest_exp_avg", C.c_void_p), ("rest_exp_avg_sq", C.c_void_p),
                 ("lr_dc", C.c_double), ("lr_rest", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("step_dc", C.c_int32), ("step_rest", C.c_int32), ("sparse", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CameraGrads(C.Structure):
+    """GsrCameraGrads of include/gsr.h (gsr_backward_preprocess_camera)."""
+    _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p), ("scratch", C.c_void_p)]
 
 
 class AdamTensor(C.Structure):
@@ -137,6 +143,12 @@ def load() -> C.CDLL:
     lib.gsr_backward_preprocess.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int,
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsr_camera_grad_scratch_bytes.restype = C.c_size_t
+    lib.gsr_camera_grad_scratch_bytes.argtypes = [C.c_int]
+    lib.gsr_backward_preprocess_camera.restype = C.c_int
+    lib.gsr_backward_preprocess_camera.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int,
+                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CameraGrads), vp]
     lib.gsr_backward_preprocess_sh_adam.restype = C.c_int
     lib.gsr_backward_preprocess_sh_adam.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                     vp, vp, vp, vp, vp, vp, C.POINTER(ShAdam), vp]

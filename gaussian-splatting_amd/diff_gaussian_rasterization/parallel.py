@@ -1,5 +1,6 @@
 """Sharding of the rasterizer across the GPUs of one node (net-new: the reference has no
-multi-GPU code).  One process per GPU, torch.distributed (backend "nccl" = RCCL over xGMI on ROCm, "gloo" in the CPU
+multi-GPU code).  None of these entry points returns camera gradients: viewmatrix / projmatrix / campos enter them
+detached, whatever their requires_grad (the single-process rasterize_gaussians(tile_rows=...) returns a band's share).  One process per GPU, torch.distributed (backend "nccl" = RCCL over xGMI on ROCm, "gloo" in the CPU
 tests).  Two modes:
 
 A. TWO-AXIS (training; `render_two_axis`, SURVEY 8(e) as specified)
@@ -216,10 +217,21 @@ def render_sharded(render_band: Callable, inputs: Sequence, plan: BandPlan, grou
     return both[:3], radii, both[3:4]
 
 
+def _camera_detached(raster_settings):
+    """The multi-GPU forms return no camera gradient: viewmatrix / projmatrix / campos enter them detached (a per-band partial camera
+    gradient without an all-reduce would be wrong, and summing it is out of scope)."""
+    t = {k: getattr(raster_settings, k) for k in ("viewmatrix", "projmatrix", "campos")}
+    if not any(isinstance(v, torch.Tensor) and v.requires_grad for v in t.values()):
+        return raster_settings
+    return raster_settings._replace(**{k: v.detach() for k, v in t.items()})
+
+
 def hip_band_renderer(raster_settings, group=None):
     """The product's band renderer: inputs = (means3D, shs, opacities, scales, rotations); the per-Gaussian 2-D
-    gradient records are all-reduced between the blend backward and the per-Gaussian backward."""
+    gradient records are all-reduced between the blend backward and the per-Gaussian backward.  The camera tensors enter
+    detached: no camera gradient (as every multi-GPU entry point of this module)."""
     from . import rasterize_gaussians
+    raster_settings = _camera_detached(raster_settings)
 
     def _sync(records: torch.Tensor):
         if _world(group) > 1:

@@ -171,6 +171,40 @@ int gsr_backward_preprocess(const GsrRasterSettings* settings, int P, int M,
                             float* dL_dscales, float* dL_drotations, void* stream);
 
 /*
+ * Camera gradients (no reference counterpart): gsr_backward_preprocess that also returns dL/d(viewmatrix), dL/d(projmatrix) and
+ * dL/d(campos).  Every other output is the same bits as gsr_backward_preprocess writes for the same inputs.
+ * Contract: the gradient of the same function whose Gaussian gradients the backward returns, under the same conventions -- the
+ * frustum-clamp stop-gradient, and no gradient through culling, radii, tile assignment, depth order or the alpha >= 1/255 and
+ * transmittance cut-offs.  Per visible Gaussian (radii > 0), with p = (x, y, z, 1) and math matrices V, P:
+ *   view rows 0-2:          dL/dV[r][j] += dt_r p_j   (dt = dL/d(view-space position), after the clamp masks), and for j < 3 the
+ *                           covariance path through T = J W:  dW0j += J00 dT0j,  dW1j += J11 dT1j,  dW2j += J02 dT0j + J12 dT1j
+ *   projection rows 0, 1, 3: dL/dP[0][j] += dhx p_j,  dL/dP[1][j] += dhy p_j,  dL/dP[3][j] += dhw p_j  (dh = dL/d(clip position))
+ *   campos:                 dL/dcampos -= the SH backward's view-direction term of dL/dmean (zero with colors_precomp)
+ *   View row 3 and projection row 2 are read by no kernel: their gradients are exactly 0.
+ * The outputs are in the layout of viewmatrix / projmatrix (flat index i + 4*j = math element (row i, col j)), so a caller that
+ * builds projmatrix = viewmatrix @ proj and campos = inverse(viewmatrix)[3, :3] chains through them with no further convention.
+ * The three outputs are OVERWRITTEN (fp32, summed in fp64 in a fixed order: bit-reproducible); P == 0 writes zeros.
+ * scratch: device memory of gsr_camera_grad_scratch_bytes(P) bytes, 8-byte aligned.  Every input form of gsr_backward_preprocess
+ * is accepted (fused SH of any M, split sh_dc, colors_precomp, cov3D_precomp, antialiasing, with or without the inverse-depth
+ * gradient in the records).  A screen-sharded caller gets its band's contribution from its own records.
+ */
+typedef struct GsrCameraGrads {
+    float* dL_dviewmatrix;    /* [16] */
+    float* dL_dprojmatrix;    /* [16] */
+    float* dL_dcampos;        /* [3] */
+    void* scratch;            /* gsr_camera_grad_scratch_bytes(P) */
+} GsrCameraGrads;
+size_t gsr_camera_grad_scratch_bytes(int P);
+int gsr_backward_preprocess_camera(const GsrRasterSettings* settings, int P, int M,
+                                   const float* means3D, const float* shs, const float* colors_precomp,
+                                   const float* opacities, const float* scales, const float* rotations,
+                                   const float* cov3D_precomp, const int32_t* radii, const void* geom_buffer,
+                                   const float* splat_grads,
+                                   float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                                   float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                   float* dL_dscales, float* dL_drotations, const GsrCameraGrads* camera, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
