@@ -162,6 +162,146 @@ def _require_cuda(t: torch.Tensor, name: str):
         raise GsrError(f"{name} must live on a HIP device ('cuda'); the MI355X rasterizer has no CPU path")
 
 
+# ---- one function per native operation of the rasterizer.  `s` is a _make_settings record (the caller keeps its tensors alive); the
+# caller holds torch.cuda.device(device).  Tensors are passed as they are: None where the C ABI takes NULL. --------------------------------
+class _Forward(NamedTuple):
+    """What a forward leaves for its blend backward: the three scratch buffers and R (num_rendered)."""
+    geom: torch.Tensor
+    binning: torch.Tensor
+    img: torch.Tensor
+    num_rendered: int
+
+
+def _rasterize_forward(s, P, M, inputs, color, invdepth, radii, device, kinds=("geom", "binning", "image")) -> _Forward:
+    """gsr_rasterize_forward.  inputs = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp); `kinds` are the
+    _Buffer kinds of the geometry, binning and image buffers."""
+    lib = _lib.load()
+    geom, binning, img = (_Buffer(device, k) for k in kinds)
+    nr = C.c_int32(0)
+    _lib.check(lib.gsr_rasterize_forward(C.byref(s), P, M, *[_ptr(t) for t in inputs], geom.cb, None, binning.cb, None, img.cb, None,
+                                         _ptr(color), _ptr(invdepth), _ptr(radii), C.byref(nr), _stream_ptr(device)),
+               "gsr_rasterize_forward")
+    return _Forward(geom.t, binning.t, img.t, int(nr.value))
+
+
+def _rasterize_records(entry: str, s, lead, records, device):
+    """gsr_rasterize_from_splats / _from_packed / _from_segments (`entry`): bins and blends projected records in the settings' band.
+    `lead` is what the entry point takes between the settings and the records: (P,) or (n_segments, capacity).
+    -> (color[3,H,W], invdepth[1,H,W], _Forward), zeros outside the band."""
+    lib = _lib.load()
+    color = torch.zeros(3, s.image_height, s.image_width, dtype=torch.float32, device=device)
+    invdepth = torch.zeros(1, s.image_height, s.image_width, dtype=torch.float32, device=device)
+    geom, binning, img = _Buffer(device, "geom"), _Buffer(device, "binning"), _Buffer(device, "image")
+    nr = C.c_int32(0)
+    args = (C.byref(s), *lead, _ptr(records), geom.cb, None, binning.cb, None, img.cb, None, _ptr(color), _ptr(invdepth), C.byref(nr),
+            _stream_ptr(device))
+    if entry == "gsr_rasterize_from_splats":
+        rc = lib.gsr_rasterize_from_splats(*args)
+    elif entry == "gsr_rasterize_from_packed":
+        rc = lib.gsr_rasterize_from_packed(*args)
+    else:
+        rc = lib.gsr_rasterize_from_segments(*args)
+    _lib.check(rc, entry)
+    return color, invdepth, _Forward(geom.t, binning.t, img.t, int(nr.value))
+
+
+def _preprocess_shard(raster_settings, tile_rows, keep: list, rows, means3D, sh, opacities, scales, rotations, dc, what: str):
+    """gsr_preprocess_forward on one shard of Gaussians (the multi-GPU modes; split SH only in degree-3 storage).
+    -> (settings, records, radii[P], M, (means3D, sh, opacities, scales, rotations, dc) as passed to the kernels).  The settings
+    (band `tile_rows`, dc) serve the caller's next calls; their tensors live in `keep`.  records: [P,16], or [rows,16] whose rows
+    past the shard are zero (records without tiles) when `rows` is given."""
+    lib = _lib.load()
+    _require_cuda(means3D, "means3D")
+    device = means3D.device
+    P = int(means3D.shape[0])
+    m_c, sh_c, op_c, sc_c, rot_c, dc_c = (_f32c(t) for t in (means3D, sh, opacities, scales, rotations, dc))
+    M = int(sh_c.shape[1]) + (1 if dc_c is not None else 0)
+    if dc_c is not None and (M != 16 or dc_c.data_ptr() % 16 or sh_c.data_ptr() % 16):
+        raise GsrError(f"{what}: the split SH form needs degree-3 storage (dc[P,1,3] + shs[P,15,3])")
+    with torch.cuda.device(device):
+        s = _make_settings(raster_settings, keep, tile_rows, False)
+        if dc_c is not None:
+            s.sh_dc = dc_c.data_ptr()
+        if rows is None:
+            records = torch.empty(P, 16, dtype=torch.float32, device=device)
+        else:
+            records = torch.zeros(int(rows), 16, dtype=torch.float32, device=device)
+        radii = torch.empty(P, dtype=torch.int32, device=device)
+        scratch = torch.empty(_sized("geom_shard", device, lib.gsr_geometry_bytes(P)), dtype=torch.uint8, device=device)
+        _lib.check(lib.gsr_preprocess_forward(C.byref(s), P, M, _ptr(m_c), _ptr(sh_c), None, _ptr(op_c), _ptr(sc_c), _ptr(rot_c), None,
+                                              _ptr(scratch), _ptr(radii), _ptr(records), _stream_ptr(device)), "gsr_preprocess_forward")
+    return s, records, radii, M, (m_c, sh_c, op_c, sc_c, rot_c, dc_c)
+
+
+def _backward_scratch(lib, P, num_rendered, device) -> torch.Tensor:
+    return torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P, num_rendered)), dtype=torch.uint8, device=device)
+
+
+def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device) -> torch.Tensor:
+    """gsr_backward_blend -> the per-Gaussian 48-byte gradient records [P,12], a view into the backward scratch."""
+    lib = _lib.load()
+    scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
+    rec_ptr = C.c_void_p(0)
+    _lib.check(lib.gsr_backward_blend(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color),
+                                      _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), _stream_ptr(device)), "gsr_backward_blend")
+    off = int(rec_ptr.value) - scratch.data_ptr()
+    return scratch[off:off + P * 48].view(torch.float32).view(P, 12)
+
+
+def _gradients(P, device, colors: bool, cov3D: bool, sh_rows, dc: bool, scales: bool, rotations: bool):
+    """The per-Gaussian backward's outputs in the order of include/gsr.h -- [dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+    dL_dcov3D, dL_dsh, dL_dscales, dL_drotations] -- and dL_d(sh_dc); the flags (sh_rows: rows of dL_dsh per Gaussian) say which of the
+    optional ones exist (None otherwise)."""
+    f = dict(dtype=torch.float32, device=device)
+    opt = lambda on, *shape: torch.empty(P, *shape, **f) if on else None      # noqa: E731
+    grads = [torch.empty(P, 3, **f), opt(colors, 3), torch.empty(P, 1, **f), torch.empty(P, 3, **f), opt(cov3D, 6),
+             opt(sh_rows is not None, sh_rows, 3), opt(scales, 3), opt(rotations, 4)]
+    return grads, opt(dc, 1, 3)
+
+
+def _backward_preprocess(s, P, M, inputs, radii, geom, records, grads, device, extra=None) -> None:
+    """The per-Gaussian backward from the [P,12] records: gsr_backward_preprocess, or with a _lib.CameraGrads `extra`
+    gsr_backward_preprocess_camera, or with a _lib.ShAdam gsr_backward_preprocess_sh_adam (which writes no colour or SH gradient: it
+    steps the two SH tensors in place).  inputs = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp),
+    grads as _gradients returns them."""
+    lib = _lib.load()
+    st = _stream_ptr(device)
+    if isinstance(extra, _lib.ShAdam):
+        m, sh, _, op, sc, rot, cov = inputs
+        dm2, _, dop, dm3, dcov, _, dsc, drot = grads
+        _lib.check(lib.gsr_backward_preprocess_sh_adam(C.byref(s), P, M, _ptr(m), _ptr(sh), _ptr(op), _ptr(sc), _ptr(rot), _ptr(cov),
+                                                       _ptr(radii), _ptr(geom), _ptr(records), _ptr(dm2), _ptr(dop), _ptr(dm3),
+                                                       _ptr(dcov), _ptr(dsc), _ptr(drot), C.byref(extra), st),
+                   "gsr_backward_preprocess_sh_adam")
+        return
+    args = (C.byref(s), P, M, *[_ptr(t) for t in inputs], _ptr(radii), _ptr(geom), _ptr(records), *[_ptr(g) for g in grads])
+    if extra is None:
+        _lib.check(lib.gsr_backward_preprocess(*args, st), "gsr_backward_preprocess")
+    else:
+        _lib.check(lib.gsr_backward_preprocess_camera(*args, C.byref(extra), st), "gsr_backward_preprocess_camera")
+
+
+def _rasterize_backward(s, P, M, inputs, radii, fwd: _Forward, g_color, g_depth, grads, device) -> None:
+    """gsr_rasterize_backward: blend backward and per-Gaussian backward in one call (arguments as _backward_preprocess)."""
+    lib = _lib.load()
+    scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
+    _lib.check(lib.gsr_rasterize_backward(C.byref(s), P, M, fwd.num_rendered, *[_ptr(t) for t in inputs], _ptr(radii), _ptr(fwd.geom),
+                                          _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color), _ptr(g_depth), *[_ptr(g) for g in grads],
+                                          _ptr(scratch), None, _stream_ptr(device)), "gsr_rasterize_backward")
+
+
+def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
+    """gsr_mark_visible -> bool[P]: in front of the near plane (the reference's checkFrustum with prefiltered = False)."""
+    lib = _lib.load()
+    _require_cuda(points, name)
+    with torch.no_grad(), torch.cuda.device(points.device):
+        pos, vm, pm = _f32c(points), _f32c(viewmatrix), _f32c(projmatrix)
+        present = torch.empty(pos.shape[0], dtype=torch.uint8, device=pos.device)
+        _lib.check(lib.gsr_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(present), _stream_ptr(pos.device)),
+                   "gsr_mark_visible")
+    return present.bool()
+
+
 # ---- opt-in: the Adam step of the two SH tensors inside the backward (gsr_backward_preprocess_sh_adam) --------------------------
 _SH_ADAM = {}      # id(rest parameter) -> _ShAdamFusion
 
@@ -233,7 +373,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None):
         # viewmatrix / projmatrix / campos: raster_settings' own tensors, passed again so that autograd sees them (camera gradients,
         # gsr_backward_preprocess_camera).  The kernels read them from raster_settings.
-        lib = _lib.load()
+        _lib.load()      # (a missing library is reported before anything else)
         _require_cuda(means3D, "means3D")
         _trim_cache_if_pending()
         device = means3D.device
@@ -273,26 +413,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                 color.zero_()
                 invdepth.zero_()
             radii = torch.empty(P, dtype=torch.int32, device=device)
-            geom, binning, img = _Buffer(device, "geom"), _Buffer(device, "binning"), _Buffer(device, "image")
-            nr = C.c_int32(0)
-            args = (C.byref(s), P, M, _ptr(means3D_c), _ptr(sh_c), _ptr(col_c), _ptr(op_c), _ptr(sc_c), _ptr(rot_c),
-                    _ptr(cov_c), geom.cb, None, binning.cb, None, img.cb, None, _ptr(color), _ptr(invdepth),
-                    _ptr(radii), C.byref(nr), _stream_ptr(device))
-            if raster_settings.debug:
-                cpu_args = _cpu_copy((means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                      raster_settings))
-                try:
-                    _lib.check(lib.gsr_rasterize_forward(*args), "gsr_rasterize_forward")
-                except Exception as ex:
+            cpu_args = _cpu_copy((means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                  raster_settings)) if raster_settings.debug else None
+            try:
+                fwd = _rasterize_forward(s, P, M, (means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c), color, invdepth, radii, device)
+            except Exception:
+                if cpu_args is not None:
                     torch.save(cpu_args, "snapshot_fw.dump")
                     print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                    raise ex
-            else:
-                _lib.check(lib.gsr_rasterize_forward(*args), "gsr_rasterize_forward")
+                raise
         ctx.raster_settings = raster_settings
         ctx.tile_rows = tile_rows
         ctx.grad_sync = grad_sync
-        ctx.num_rendered = int(nr.value)
+        ctx.num_rendered = fwd.num_rendered
         global _last_R, _max_R
         _last_R = ctx.num_rendered
         _max_R = max(_max_R, _last_R)
@@ -318,7 +451,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                               sc_c if sc_c is not None else means3D_c.new_empty(0),
                               rot_c if rot_c is not None else means3D_c.new_empty(0),
                               cov_c if cov_c is not None else means3D_c.new_empty(0),
-                              radii, geom.t, binning.t, img.t,
+                              radii, fwd.geom, fwd.binning, fwd.img,
                               dc_c if dc_c is not None else means3D_c.new_empty(0))
         ctx.mark_non_differentiable(radii)
         # an output nobody differentiates through (the inverse-depth image unless depth supervision is on, train.py:130-137)
@@ -339,95 +472,51 @@ class _RasterizeGaussians(torch.autograd.Function):
         device = means3D.device
         P = int(means3D.shape[0])
         M = ctx.M
-        f = dict(dtype=torch.float32, device=device)
-        dL_dmeans2D = torch.empty(P, 3, **f)
-        dL_dcolors = torch.empty(P, 3, **f) if has_col else None      # intermediates of the kernel unless they are inputs' grads
-        dL_dopacity = torch.empty(P, 1, **f)
-        dL_dmeans3D = torch.empty(P, 3, **f)
-        dL_dcov3D = torch.empty(P, 6, **f) if has_cov else None
         has_dc = ctx.has_dc
         fused_adam = ctx.sh_adam if (ctx.sh_adam is not None and _SH_ADAM.get(ctx.sh_adam.key) is ctx.sh_adam) else None
-        dL_dsh = torch.empty(P, M - 1 if has_dc else M, 3, **f) if (has_sh and fused_adam is None) else None
-        dL_ddc = torch.empty(P, 1, 3, **f) if (has_dc and fused_adam is None) else None
-        dL_dscales = torch.empty(P, 3, **f) if has_sc else None
-        dL_drot = torch.empty(P, 4, **f) if has_rot else None
+        # (intermediates of the kernel unless they are inputs' grads: dL_dcolors, dL_dcov3D)
+        grads, dL_ddc = _gradients(P, device, has_col, has_cov, (M - 1 if has_dc else M) if (has_sh and fused_adam is None) else None,
+                                   has_dc and fused_adam is None, has_sc, has_rot)
         cam_out = cam_scratch = None
         if ctx.camera_grad:      # [16] view, [16] projection, [3] campos (64-byte offsets), fp32
-            cam_out = torch.zeros(48, **f)
+            cam_out = torch.zeros(48, dtype=torch.float32, device=device)
             cam_scratch = torch.empty(max(int(lib.gsr_camera_grad_scratch_bytes(P)), 8), dtype=torch.uint8, device=device)
         if P > 0:
             g_color = _f32c(grad_out_color)
-            g_depth = _f32c(grad_out_depth) if grad_out_depth is not None else None
-            scratch = torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P, ctx.num_rendered)), dtype=torch.uint8,
-                                  device=device)
+            g_depth = _f32c(grad_out_depth)
             keep: list = []
             with torch.cuda.device(device):
                 s = _make_settings(rs, keep, ctx.tile_rows)
                 if has_dc:
                     s.sh_dc = dc.data_ptr()
                     s.dL_dsh_dc = dL_ddc.data_ptr() if dL_ddc is not None else None
-                st = _stream_ptr(device)
-                inputs = (_ptr(means3D), _ptr(sh) if has_sh else None, _ptr(col) if has_col else None, _ptr(op),
-                          _ptr(sc) if has_sc else None, _ptr(rot) if has_rot else None, _ptr(cov) if has_cov else None,
-                          _ptr(radii))
-                outs = (_ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                        _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drot))
-
-                def _run():
-                    if fused_adam is not None:
-                        # blend backward, then the per-Gaussian backward that steps the two SH tensors in place
-                        rec_ptr = C.c_void_p(0)
-                        _lib.check(lib.gsr_backward_blend(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img),
-                                                          _ptr(g_color), _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), st),
-                                   "gsr_backward_blend")
-                        adam = fused_adam.arm()
-                        _lib.check(lib.gsr_backward_preprocess_sh_adam(
-                            C.byref(s), P, M, _ptr(means3D), _ptr(sh), _ptr(op), _ptr(sc) if has_sc else None,
-                            _ptr(rot) if has_rot else None, _ptr(cov) if has_cov else None, _ptr(radii), _ptr(geom), rec_ptr,
-                            _ptr(dL_dmeans2D), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dscales),
-                            _ptr(dL_drot), C.byref(adam), st), "gsr_backward_preprocess_sh_adam")
-                        return
-                    if ctx.camera_grad:
-                        # blend backward, (multi-GPU: record sum), then the per-Gaussian backward that also sums the camera gradient
-                        rec_ptr = C.c_void_p(0)
-                        _lib.check(lib.gsr_backward_blend(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img),
-                                                          _ptr(g_color), _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), st),
-                                   "gsr_backward_blend")
+                inputs = (means3D, sh if has_sh else None, col if has_col else None, op, sc if has_sc else None, rot if has_rot else None,
+                          cov if has_cov else None)
+                fwd = _Forward(geom, binning, img, ctx.num_rendered)
+                cpu_args = _cpu_copy((means3D, radii, col, sc, rot, cov, sh, grad_out_color, rs)) if rs.debug else None
+                try:
+                    if fused_adam is None and not ctx.camera_grad and ctx.grad_sync is None:
+                        _rasterize_backward(s, P, M, inputs, radii, fwd, g_color, g_depth, grads, device)
+                    else:
+                        # blend backward -> (multi-GPU: sum of the 48-byte per-Gaussian records across ranks, parallel.py) -> the
+                        # per-Gaussian backward that also sums the camera gradient, or steps the two SH tensors in place
+                        records = _backward_blend(s, P, fwd, g_color, g_depth, device)
                         if ctx.grad_sync is not None:
-                            off = int(rec_ptr.value) - scratch.data_ptr()
-                            ctx.grad_sync(scratch[off:off + P * 48].view(torch.float32).view(P, 12))
-                        camg = _lib.CameraGrads(cam_out.data_ptr(), cam_out.data_ptr() + 64, cam_out.data_ptr() + 128,
-                                                cam_scratch.data_ptr())
-                        _lib.check(lib.gsr_backward_preprocess_camera(C.byref(s), P, M, *inputs, _ptr(geom), rec_ptr, *outs,
-                                                                      C.byref(camg), st), "gsr_backward_preprocess_camera")
-                        return
-                    if ctx.grad_sync is None:
-                        _lib.check(lib.gsr_rasterize_backward(C.byref(s), P, M, ctx.num_rendered, *inputs, _ptr(geom),
-                                                              _ptr(binning), _ptr(img), _ptr(g_color), _ptr(g_depth), *outs,
-                                                              _ptr(scratch), None, st), "gsr_rasterize_backward")
-                        return
-                    # screen-sharded training: blend backward on the own band -> sum the 48-byte per-Gaussian records
-                    # across ranks -> per-Gaussian backward (parallel.py)
-                    rec_ptr = C.c_void_p(0)
-                    _lib.check(lib.gsr_backward_blend(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img),
-                                                      _ptr(g_color), _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), st),
-                               "gsr_backward_blend")
-                    off = int(rec_ptr.value) - scratch.data_ptr()
-                    records = scratch[off:off + P * 48].view(torch.float32).view(P, 12)
-                    ctx.grad_sync(records)
-                    _lib.check(lib.gsr_backward_preprocess(C.byref(s), P, M, *inputs, _ptr(geom), _ptr(records), *outs, st),
-                               "gsr_backward_preprocess")
-
-                if rs.debug:
-                    cpu_args = _cpu_copy((means3D, radii, col, sc, rot, cov, sh, grad_out_color, rs))
-                    try:
-                        _run()
-                    except Exception as ex:
+                            ctx.grad_sync(records)
+                        if fused_adam is not None:
+                            extra = fused_adam.arm()
+                        elif ctx.camera_grad:
+                            extra = _lib.CameraGrads(cam_out.data_ptr(), cam_out.data_ptr() + 64, cam_out.data_ptr() + 128,
+                                                     cam_scratch.data_ptr())
+                        else:
+                            extra = None
+                        _backward_preprocess(s, P, M, inputs, radii, geom, records, grads, device, extra)
+                except Exception:
+                    if cpu_args is not None:
                         torch.save(cpu_args, "snapshot_bw.dump")
                         print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                        raise ex
-                else:
-                    _run()
+                    raise
+        dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drot = grads
         dL_dopacity = dL_dopacity.view(ctx.op_shape)
         if ctx.dc_mode == "as_sh":      # the DC tensor travelled as the fused [P,1,3] form
             dL_ddc = dL_dsh.view(ctx.dc_shape)
@@ -471,16 +560,7 @@ class GaussianRasterizer(nn.Module):
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """bool[P]: in front of the near plane (the reference's mark_visible / checkFrustum)."""
-        lib = _lib.load()
-        _require_cuda(positions, "positions")
-        rs = self.raster_settings
-        with torch.no_grad(), torch.cuda.device(positions.device):
-            pos = _f32c(positions)
-            vm, pm = _f32c(rs.viewmatrix), _f32c(rs.projmatrix)
-            present = torch.empty(pos.shape[0], dtype=torch.uint8, device=pos.device)
-            _lib.check(lib.gsr_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(present),
-                                            _stream_ptr(pos.device)), "gsr_mark_visible")
-        return present.bool()
+        return _mark_visible(positions, "positions", self.raster_settings.viewmatrix, self.raster_settings.projmatrix)
 
     def forward(self, means3D, means2D, opacities, dc=None, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):

@@ -41,20 +41,6 @@ class GsrForwardViews(C.Structure):
 
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
-EXPORTS = [
-    "gsr_abi_version", "gsr_last_error", "gsr_geometry_bytes", "gsr_binning_bytes", "gsr_image_bytes",
-    "gsr_backward_scratch_bytes",
-    "gsr_rasterize_forward", "gsr_rasterize_backward", "gsr_backward_blend", "gsr_backward_preprocess",
-    "gsr_camera_grad_scratch_bytes", "gsr_backward_preprocess_camera",
-    "gsr_preprocess_forward", "gsr_rasterize_from_splats",
-    "gsr_route_scratch_bytes", "gsr_route_count", "gsr_route_pack", "gsr_rasterize_from_packed", "gsr_route_return",
-    "gsr_route_pack_fixed", "gsr_rasterize_from_segments",
-    "gsr_mark_visible", "gsr_forward_views", "gsr_adam_step", "gsr_adam_step_multi", "gsr_backward_preprocess_sh_adam", "gsr_sparse_adam_step", "gsr_sparse_adam_step_multi", "gsr_ssim_forward", "gsr_ssim_backward",
-    "gsr_knn_scratch_bytes", "gsr_knn_mean_dist2", "gsr_ssim_partial_count", "gsr_ssim_mean_forward", "gsr_ssim_mean_backward",
-    "gsr_train_loss_forward", "gsr_train_loss_backward", "gsr_density_stats",
-    "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_profile_counters", "gsr_profile_trace", "gsr_set_option",
-]
-
 _lib: Optional[C.CDLL] = None
 
 
@@ -91,6 +77,62 @@ class SparseAdamTensor(C.Structure):
                 ("lr", C.c_double), ("eps", C.c_double)]
 
 
+_vp, _i32p, _i64p, _RS = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(GsrRasterSettings)
+_BUFFERS = [RESIZE_FN, _vp] * 3      # geometry, binning and image buffer: resize callback + user pointer each
+_RECORDS_OUT = _BUFFERS + [_vp, _vp, _i32p, _vp]      # out_color, out_invdepth, num_rendered, stream
+
+# name -> (restype, argtypes) of every function include/gsr.h declares, in its parameter order (tests/test_abi_cpu.py holds the arities to
+# the header)
+SIGNATURES = {
+    "gsr_abi_version": (C.c_int, []),
+    "gsr_last_error": (C.c_char_p, []),
+    "gsr_geometry_bytes": (C.c_size_t, [C.c_int]),
+    "gsr_binning_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "gsr_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gsr_backward_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "gsr_rasterize_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 7 + _BUFFERS + [_vp, _vp, _vp, _i32p, _vp]),
+    "gsr_rasterize_backward": (C.c_int, [_RS, C.c_int, C.c_int, C.c_int32] + [_vp] * 8 + [_vp] * 5 + [_vp] * 9
+                               + [C.POINTER(C.c_void_p), _vp]),
+    "gsr_backward_blend": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), _vp]),
+    "gsr_backward_preprocess": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 10 + [_vp] * 9),
+    "gsr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "gsr_backward_preprocess_camera": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 10 + [_vp] * 8 + [C.POINTER(CameraGrads), _vp]),
+    "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
+    "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
+    "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gsr_route_count": (C.c_int, [C.c_int, _vp, C.c_int, _i32p, _vp, _vp, _vp]),
+    "gsr_route_pack": (C.c_int, [C.c_int, _vp, C.c_int, _i32p, _i64p, _vp, _vp, _vp, _vp]),
+    "gsr_rasterize_from_packed": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
+    "gsr_route_return": (C.c_int, [C.c_int, C.c_int, _i64p, _vp, _vp, _vp, _vp]),
+    "gsr_route_pack_fixed": (C.c_int, [C.c_int, _vp, C.c_int, _i32p, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_rasterize_from_segments": (C.c_int, [_RS, C.c_int, C.c_int, _vp] + _RECORDS_OUT),
+    "gsr_backward_preprocess_sh_adam": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 9 + [_vp] * 6 + [C.POINTER(ShAdam), _vp]),
+    "gsr_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _vp]),
+    "gsr_adam_step_multi": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, _vp]),
+    "gsr_sparse_adam_step": (C.c_int, [_vp] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    "gsr_sparse_adam_step_multi": (C.c_int, [C.POINTER(SparseAdamTensor), C.c_int32, _vp, C.c_int64, C.c_double, C.c_double, _vp]),
+    "gsr_density_stats": (C.c_int, [C.c_int] + [_vp] * 7),
+    "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),
+    "gsr_ssim_backward": (C.c_int, [C.c_int] * 3 + [_vp] * 8),
+    "gsr_ssim_partial_count": (C.c_int64, [C.c_int] * 3),
+    "gsr_ssim_mean_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 8),
+    "gsr_ssim_mean_backward": (C.c_int, [C.c_int] * 3 + [_vp] * 8),
+    "gsr_train_loss_forward": (C.c_int, [C.c_int] * 3 + [_vp, _vp, C.c_float] + [_vp] * 6),
+    "gsr_train_loss_backward": (C.c_int, [C.c_int] * 3 + [_vp, _vp, _vp, C.c_float] + [_vp] * 5),
+    "gsr_mark_visible": (C.c_int, [C.c_int] + [_vp] * 5),
+    "gsr_forward_views": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(GsrForwardViews)]),
+    "gsr_profile_enable": (C.c_int, [C.c_int]),
+    "gsr_profile_reset": (C.c_int, []),
+    "gsr_profile_read": (C.c_int, [C.POINTER(C.c_float), _i32p, C.c_int]),
+    "gsr_profile_counters": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int]),
+    "gsr_profile_trace": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+    "gsr_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+}
+EXPORTS = list(SIGNATURES)
+
+
 def load() -> C.CDLL:
     """Load libgsr_hip.so.  torch must own the HIP runtime: torch bundles its own libamdhip64.so (SONAME
     libamdhip64.so.7) and our library NEEDs the same SONAME, so importing torch first makes both resolve to
@@ -110,118 +152,17 @@ def load() -> C.CDLL:
     lib.gsr_abi_version.restype = C.c_int
     # the version is checked BEFORE any other symbol is bound: an older library (tools/build_prev_lib.sh, GSR_LIB=...) fails
     # with this message instead of an AttributeError on a symbol it does not have yet
-    if lib.gsr_abi_version() != ABI_VERSION and os.environ.get("GSR_ALLOW_ABI_MISMATCH") != "1":
+    mismatch_ok = os.environ.get("GSR_ALLOW_ABI_MISMATCH") == "1"
+    if lib.gsr_abi_version() != ABI_VERSION and not mismatch_ok:
         raise GsrError(f"{path}: ABI version {lib.gsr_abi_version()} != {ABI_VERSION} (set GSR_ALLOW_ABI_MISMATCH=1 to bind the "
                        f"symbols both versions share, for A/B runs of an older revision)")
     missing = [n for n in EXPORTS if not hasattr(lib, n)]
-    if missing and os.environ.get("GSR_ALLOW_ABI_MISMATCH") != "1":
+    if missing and not mismatch_ok:
         raise GsrError(f"{path} does not export {missing}")
-    lib.gsr_last_error.restype = C.c_char_p
-    lib.gsr_geometry_bytes.restype = C.c_size_t
-    lib.gsr_geometry_bytes.argtypes = [C.c_int]
-    lib.gsr_binning_bytes.restype = C.c_size_t
-    lib.gsr_binning_bytes.argtypes = [C.c_int64, C.c_int]
-    lib.gsr_image_bytes.restype = C.c_size_t
-    lib.gsr_image_bytes.argtypes = [C.c_int, C.c_int]
-    lib.gsr_backward_scratch_bytes.restype = C.c_size_t
-    lib.gsr_backward_scratch_bytes.argtypes = [C.c_int, C.c_int64]
-    vp = C.c_void_p
-    lib.gsr_rasterize_forward.restype = C.c_int
-    lib.gsr_rasterize_forward.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int,
-                                          vp, vp, vp, vp, vp, vp, vp,
-                                          RESIZE_FN, vp, RESIZE_FN, vp, RESIZE_FN, vp,
-                                          vp, vp, vp, C.POINTER(C.c_int32), vp]
-    lib.gsr_rasterize_backward.restype = C.c_int
-    lib.gsr_rasterize_backward.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int, C.c_int32,
-                                           vp, vp, vp, vp, vp, vp, vp, vp,
-                                           vp, vp, vp, vp, vp,
-                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_void_p), vp]
-    lib.gsr_backward_blend.restype = C.c_int
-    lib.gsr_backward_blend.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int32, vp, vp, vp, vp, vp, vp,
-                                       C.POINTER(C.c_void_p), vp]
-    lib.gsr_backward_preprocess.restype = C.c_int
-    lib.gsr_backward_preprocess.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int,
-                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                            vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_camera_grad_scratch_bytes.restype = C.c_size_t
-    lib.gsr_camera_grad_scratch_bytes.argtypes = [C.c_int]
-    lib.gsr_backward_preprocess_camera.restype = C.c_int
-    lib.gsr_backward_preprocess_camera.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int,
-                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                   vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CameraGrads), vp]
-    lib.gsr_backward_preprocess_sh_adam.restype = C.c_int
-    lib.gsr_backward_preprocess_sh_adam.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                    vp, vp, vp, vp, vp, vp, C.POINTER(ShAdam), vp]
-    lib.gsr_preprocess_forward.restype = C.c_int
-    lib.gsr_preprocess_forward.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_rasterize_from_splats.restype = C.c_int
-    lib.gsr_rasterize_from_splats.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, vp, RESIZE_FN, vp, RESIZE_FN, vp,
-                                              RESIZE_FN, vp, vp, vp, C.POINTER(C.c_int32), vp]
-    if not missing or "gsr_route_count" not in missing:
-        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        lib.gsr_route_scratch_bytes.restype = C.c_size_t
-        lib.gsr_route_scratch_bytes.argtypes = [C.c_int, C.c_int]
-        lib.gsr_route_count.restype = C.c_int
-        lib.gsr_route_count.argtypes = [C.c_int, vp, C.c_int, i32p, vp, vp, vp]
-        lib.gsr_route_pack.restype = C.c_int
-        lib.gsr_route_pack.argtypes = [C.c_int, vp, C.c_int, i32p, i64p, vp, vp, vp, vp]
-        lib.gsr_rasterize_from_packed.restype = C.c_int
-        lib.gsr_rasterize_from_packed.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, vp, RESIZE_FN, vp, RESIZE_FN, vp,
-                                                  RESIZE_FN, vp, vp, vp, C.POINTER(C.c_int32), vp]
-        lib.gsr_route_return.restype = C.c_int
-        lib.gsr_route_return.argtypes = [C.c_int, C.c_int, i64p, vp, vp, vp, vp]
-    if not missing or "gsr_route_pack_fixed" not in missing:
-        i32p = C.POINTER(C.c_int32)
-        lib.gsr_route_pack_fixed.restype = C.c_int
-        lib.gsr_route_pack_fixed.argtypes = [C.c_int, vp, C.c_int, i32p, C.c_int, vp, vp, vp, vp, vp]
-        lib.gsr_rasterize_from_segments.restype = C.c_int
-        lib.gsr_rasterize_from_segments.argtypes = [C.POINTER(GsrRasterSettings), C.c_int, C.c_int, vp, RESIZE_FN, vp, RESIZE_FN, vp,
-                                                    RESIZE_FN, vp, vp, vp, C.POINTER(C.c_int32), vp]
-    lib.gsr_adam_step.restype = C.c_int
-    lib.gsr_adam_step.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, vp]
-    lib.gsr_adam_step_multi.restype = C.c_int
-    lib.gsr_adam_step_multi.argtypes = [C.POINTER(AdamTensor), C.c_int32, vp]
-    lib.gsr_sparse_adam_step.restype = C.c_int
-    lib.gsr_sparse_adam_step.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
-                                         C.c_double, vp]
-    lib.gsr_sparse_adam_step_multi.restype = C.c_int
-    lib.gsr_sparse_adam_step_multi.argtypes = [C.POINTER(SparseAdamTensor), C.c_int32, vp, C.c_int64, C.c_double, C.c_double, vp]
-    lib.gsr_knn_scratch_bytes.restype = C.c_size_t
-    lib.gsr_knn_scratch_bytes.argtypes = [C.c_int]
-    lib.gsr_knn_mean_dist2.restype = C.c_int
-    lib.gsr_knn_mean_dist2.argtypes = [C.c_int, vp, vp, vp, vp]
-    lib.gsr_ssim_forward.restype = C.c_int
-    lib.gsr_ssim_forward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_ssim_partial_count.restype = C.c_int64
-    lib.gsr_ssim_partial_count.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.gsr_ssim_mean_forward.restype = C.c_int
-    lib.gsr_ssim_mean_forward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_ssim_mean_backward.restype = C.c_int
-    lib.gsr_ssim_mean_backward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(lib, "gsr_train_loss_forward"):
-        lib.gsr_train_loss_forward.restype = C.c_int
-        lib.gsr_train_loss_forward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]
-        lib.gsr_train_loss_backward.restype = C.c_int
-        lib.gsr_train_loss_backward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
-    if hasattr(lib, "gsr_density_stats"):
-        lib.gsr_density_stats.restype = C.c_int
-        lib.gsr_density_stats.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_ssim_backward.restype = C.c_int
-    lib.gsr_ssim_backward.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.gsr_mark_visible.restype = C.c_int
-    lib.gsr_mark_visible.argtypes = [C.c_int, vp, vp, vp, vp, vp]
-    lib.gsr_forward_views.restype = C.c_int
-    lib.gsr_forward_views.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.POINTER(GsrForwardViews)]
-    lib.gsr_profile_enable.restype = C.c_int
-    lib.gsr_profile_enable.argtypes = [C.c_int]
-    lib.gsr_profile_reset.restype = C.c_int
-    lib.gsr_profile_read.restype = C.c_int
-    lib.gsr_profile_read.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int]
-    if hasattr(lib, "gsr_profile_counters"):
-        lib.gsr_profile_counters.restype = C.c_int
-        lib.gsr_profile_counters.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
-    lib.gsr_set_option.restype = C.c_int
-    lib.gsr_set_option.argtypes = [C.c_char_p, C.c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name not in missing:
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     # measurement hook: GSR_OPTIONS="name=value,name=value" applies gsr_set_option switches at load time (A/B runs of the
     # test-suite and of bench.py without editing them); unknown names raise
@@ -229,7 +170,6 @@ def load() -> C.CDLL:
         k, v = kv.split("=")
         check(lib.gsr_set_option(k.strip().encode(), int(v)), f"GSR_OPTIONS {kv}")
     return lib
-
 
 def check(rc: int, what: str) -> None:
     if rc != GSR_OK:
@@ -250,11 +190,8 @@ def profile_enable(on, counters: bool = False, trace: bool = False) -> None:
 def profile_trace(max_waves: int = 65536):
     """[n, 4] uint64: start, end (100 MHz ticks), placement (HW_ID | XCC << 32 | kernel << 40), steps of the most recent blend launches' waves."""
     import numpy as np
-    lib = load()
-    lib.gsr_profile_trace.restype = C.c_int
-    lib.gsr_profile_trace.argtypes = [C.POINTER(C.c_uint64), C.c_int]
     buf = np.zeros((max_waves, 4), dtype=np.uint64)
-    n = lib.gsr_profile_trace(buf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_waves))
+    n = load().gsr_profile_trace(buf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_waves))
     if n < 0:
         raise GsrError("gsr_profile_trace failed")
     return buf[:n]

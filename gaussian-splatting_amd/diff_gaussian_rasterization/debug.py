@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from . import _Buffer, _f32c, _make_settings, _ptr, _stream_ptr, GaussianRasterizationSettings
+from . import _f32c, _make_settings, _ptr, _rasterize_forward, GaussianRasterizationSettings
 
 
 def _view(buf: torch.Tensor, ptr: int, nbytes: int, dtype) -> torch.Tensor:
@@ -35,32 +35,26 @@ def forward_with_views(rs: GaussianRasterizationSettings, means3D, opacities, sh
         color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
         invdepth = torch.zeros(1, H, W, dtype=torch.float32, device=device) if want_invdepth else None
         radii = torch.empty(P, dtype=torch.int32, device=device)
-        geom, binning, img = _Buffer(device), _Buffer(device), _Buffer(device)
-        nr = C.c_int32(0)
-        _lib.check(lib.gsr_rasterize_forward(C.byref(s), P, M, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), _ptr(t[4]),
-                                             _ptr(t[5]), _ptr(t[6]), geom.cb, None, binning.cb, None, img.cb, None,
-                                             _ptr(color), _ptr(invdepth), _ptr(radii), C.byref(nr), _stream_ptr(device)),
-                   "gsr_rasterize_forward")
-        R = int(nr.value)
+        geom, binning, img, R = _rasterize_forward(s, P, M, t, color, invdepth, radii, device, kinds=("state",) * 3)
         out = {"color": color, "invdepth": invdepth, "radii": radii, "R": R,
-               "buffers": (geom.t, binning.t, img.t)}
+               "buffers": (geom, binning, img)}
         if P == 0:
             return out
         v = _lib.GsrForwardViews()
-        _lib.check(lib.gsr_forward_views(P, R, W, H, _ptr(geom.t), _ptr(binning.t), _ptr(img.t), C.byref(v)),
+        _lib.check(lib.gsr_forward_views(P, R, W, H, _ptr(geom), _ptr(binning), _ptr(img), C.byref(v)),
                    "gsr_forward_views")
         gx, gy = (W + 15) // 16, (H + 15) // 16
-        out["splats"] = _view(geom.t, v.splats, P * 64, torch.float32).view(P, 16)
-        out["tiles_touched"] = _view(geom.t, v.tiles_touched, P * 4, torch.int32)
-        out["depth_order"] = _view(geom.t, v.depth_order, P * 4, torch.int32)
+        out["splats"] = _view(geom, v.splats, P * 64, torch.float32).view(P, 16)
+        out["tiles_touched"] = _view(geom, v.tiles_touched, P * 4, torch.int32)
+        out["depth_order"] = _view(geom, v.depth_order, P * 4, torch.int32)
         if v.tile_scan:      # (ABI 4; absent when an older library is bound for an A/B run)
-            out["offsets"] = _view(geom.t, v.tile_scan, P * 4, torch.int32)
-        out["point_list"] = (_view(binning.t, v.point_list, R * 4, torch.int32) if R > 0
+            out["offsets"] = _view(geom, v.tile_scan, P * 4, torch.int32)
+        out["point_list"] = (_view(binning, v.point_list, R * 4, torch.int32) if R > 0
                              else torch.empty(0, dtype=torch.int32, device=device))
-        out["ranges"] = _view(img.t, v.ranges, gx * gy * 8, torch.int32).view(gx * gy, 2)
+        out["ranges"] = _view(img, v.ranges, gx * gy * 8, torch.int32).view(gx * gy, 2)
         if not no_backward:
-            out["final_T"] = _view(img.t, v.final_T, H * W * 4, torch.float32).view(H, W)
-            out["n_contrib"] = _view(img.t, v.n_contrib, H * W * 4, torch.int32).view(H, W)
+            out["final_T"] = _view(img, v.final_T, H * W * 4, torch.float32).view(H, W)
+            out["n_contrib"] = _view(img, v.n_contrib, H * W * 4, torch.int32).view(H, W)
     return out
 
 

@@ -1,7 +1,7 @@
 """Sharding of the rasterizer across the GPUs of one node (net-new: the reference has no
 multi-GPU code).  None of these entry points returns camera gradients: viewmatrix / projmatrix / campos enter them
 detached, whatever their requires_grad (the single-process rasterize_gaussians(tile_rows=...) returns a band's share).  One process per GPU, torch.distributed (backend "nccl" = RCCL over xGMI on ROCm, "gloo" in the CPU
-tests).  Two modes:
+tests).  Three modes:
 
 A. TWO-AXIS (training; `render_two_axis`, SURVEY 8(e) as specified)
   * Gaussian axis: rank g owns P/G Gaussians -- parameters, optimizer state, the per-Gaussian forward
@@ -39,11 +39,19 @@ and the oracle (tests/test_parallel_gloo.py); `hip_band_renderer` and `_TwoAxisH
 """
 from __future__ import annotations
 
+import ctypes as C
+import sys
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
+from . import (_Forward, _backward_blend, _backward_preprocess, _f32c, _gradients, _make_settings, _preprocess_shard, _ptr,
+               _rasterize_records, rasterize_gaussians)
+
+_pkg = sys.modules[__package__]      # (`_stream_ptr` is looked up on the package at call time, like its own code does)
 
 TILE = 16
 
@@ -230,7 +238,6 @@ def hip_band_renderer(raster_settings, group=None):
     """The product's band renderer: inputs = (means3D, shs, opacities, scales, rotations); the per-Gaussian 2-D
     gradient records are all-reduced between the blend backward and the per-Gaussian backward.  The camera tensors enter
     detached: no camera gradient (as every multi-GPU entry point of this module)."""
-    from . import rasterize_gaussians
     raster_settings = _camera_detached(raster_settings)
 
     def _sync(records: torch.Tensor):
@@ -326,89 +333,47 @@ class _TwoAxisHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacities, scales, rotations, raster_settings, band, P_pad, group, dc):
-        import ctypes as C
-        from . import _lib, _Buffer, _sized, _f32c, _make_settings, _ptr, _stream_ptr, _require_cuda
-        lib = _lib.load()
-        _require_cuda(means3D, "means3D")
-        device = means3D.device
-        P = int(means3D.shape[0])
         world = _world(group)
-        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
-        m_c, sh_c, op_c, sc_c, rot_c, dc_c = (_f32c(t) for t in (means3D, sh, opacities, scales, rotations, dc))
-        M = int(sh_c.shape[1]) + (1 if dc_c is not None else 0)
-        if dc_c is not None and (M != 16 or dc_c.data_ptr() % 16 or sh_c.data_ptr() % 16):
-            raise _lib.GsrError("two-axis renderer: the split SH form needs degree-3 storage (dc[P,1,3] + shs[P,15,3])")
         keep: list = []
+        s, records, radii, M, (m_c, sh_c, op_c, sc_c, rot_c, dc_c) = _preprocess_shard(
+            raster_settings, band, keep, int(P_pad), means3D, sh, opacities, scales, rotations, dc, "two-axis renderer")
+        device = m_c.device
         with torch.cuda.device(device):
-            st = _stream_ptr(device)
-            s = _make_settings(raster_settings, keep, band, False)
-            if dc_c is not None:
-                s.sh_dc = dc_c.data_ptr()
-            records = torch.zeros(int(P_pad), 16, dtype=torch.float32, device=device)     # padding rows: no tiles
-            radii = torch.empty(P, dtype=torch.int32, device=device)
-            scratch = torch.empty(_sized("geom_shard", device, lib.gsr_geometry_bytes(P)), dtype=torch.uint8, device=device)
-            _lib.check(lib.gsr_preprocess_forward(C.byref(s), P, M, _ptr(m_c), _ptr(sh_c), None, _ptr(op_c), _ptr(sc_c),
-                                                  _ptr(rot_c), None, _ptr(scratch), _ptr(radii), _ptr(records), st),
-                       "gsr_preprocess_forward")
             if world > 1:
                 all_records = torch.empty(world * int(P_pad), 16, dtype=torch.float32, device=device)
                 dist.all_gather_into_tensor(all_records.view(-1), records.view(-1), group=group)
             else:
                 all_records = records
             P_all = int(all_records.shape[0])
-            color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
-            invdepth = torch.zeros(1, H, W, dtype=torch.float32, device=device)
-            geom, binning, img = _Buffer(device, "geom"), _Buffer(device, "binning"), _Buffer(device, "image")
-            nr = C.c_int32(0)
-            _lib.check(lib.gsr_rasterize_from_splats(C.byref(s), P_all, _ptr(all_records), geom.cb, None, binning.cb, None,
-                                                     img.cb, None, _ptr(color), _ptr(invdepth), C.byref(nr), st),
-                       "gsr_rasterize_from_splats")
+            color, invdepth, fwd = _rasterize_records("gsr_rasterize_from_splats", s, (P_all,), all_records, device)
         ctx.raster_settings, ctx.band, ctx.group, ctx.P_pad, ctx.P_all, ctx.M = raster_settings, band, group, int(P_pad), P_all, M
-        ctx.num_rendered = int(nr.value)
+        ctx.num_rendered = fwd.num_rendered
         ctx.has_means2D = means2D is not None
         ctx.has_dc = dc_c is not None
         ctx.op_shape = tuple(opacities.shape)
         ctx.dc_shape = tuple(dc.shape) if dc is not None else None
-        ctx.save_for_backward(m_c, sh_c, op_c, sc_c, rot_c, radii, geom.t, binning.t, img.t,
+        ctx.save_for_backward(m_c, sh_c, op_c, sc_c, rot_c, radii, fwd.geom, fwd.binning, fwd.img,
                               dc_c if dc_c is not None else m_c.new_empty(0))
         ctx.mark_non_differentiable(radii)
         return color, radii, invdepth
 
     @staticmethod
     def backward(ctx, g_color, g_radii, g_depth):
-        import ctypes as C
-        from . import _lib, _sized, _f32c, _make_settings, _ptr, _stream_ptr
-        lib = _lib.load()
         m, sh, op, sc, rot, radii, geom, binning, img, dc = ctx.saved_tensors
         device = m.device
         P, P_pad, P_all, M = int(m.shape[0]), ctx.P_pad, ctx.P_all, ctx.M
-        f = dict(dtype=torch.float32, device=device)
-        d_m2, d_col, d_op = torch.empty(P, 3, **f), torch.empty(P, 3, **f), torch.empty(P, 1, **f)
-        d_m3, d_cov = torch.empty(P, 3, **f), torch.empty(P, 6, **f)
-        d_sh = torch.empty(P, M - 1 if ctx.has_dc else M, 3, **f)
-        d_dc = torch.empty(P, 1, 3, **f) if ctx.has_dc else None
-        d_sc, d_rot = torch.empty(P, 3, **f), torch.empty(P, 4, **f)
+        grads, d_dc = _gradients(P, device, True, True, M - 1 if ctx.has_dc else M, ctx.has_dc, True, True)
         keep: list = []
         with torch.cuda.device(device):
-            st = _stream_ptr(device)
             s = _make_settings(ctx.raster_settings, keep, ctx.band)
             if ctx.has_dc:
                 s.sh_dc, s.dL_dsh_dc = dc.data_ptr(), d_dc.data_ptr()
-            scratch = torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P_all, ctx.num_rendered)), dtype=torch.uint8, device=device)
-            rec_ptr = C.c_void_p(0)
-            gc = _f32c(g_color)
-            gd = _f32c(g_depth) if g_depth is not None else None
-            _lib.check(lib.gsr_backward_blend(C.byref(s), P_all, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img), _ptr(gc),
-                                              _ptr(gd), _ptr(scratch), C.byref(rec_ptr), st), "gsr_backward_blend")
-            off = int(rec_ptr.value) - scratch.data_ptr()
-            full = scratch[off:off + P_all * 48].view(torch.float32).view(P_all, 12)
-            mine = torch.empty(P_pad, 12, **f)
+            full = _backward_blend(s, P_all, _Forward(geom, binning, img, ctx.num_rendered), _f32c(g_color), _f32c(g_depth), device)
+            mine = torch.empty(P_pad, 12, dtype=torch.float32, device=device)
             _reduce_scatter_rows(full, mine, ctx.group)
             if P > 0:
-                _lib.check(lib.gsr_backward_preprocess(C.byref(s), P, M, _ptr(m), _ptr(sh), None, _ptr(op), _ptr(sc), _ptr(rot),
-                                                       None, _ptr(radii), None, _ptr(mine), _ptr(d_m2), _ptr(d_col), _ptr(d_op),
-                                                       _ptr(d_m3), _ptr(d_cov), _ptr(d_sh), _ptr(d_sc), _ptr(d_rot), st),
-                           "gsr_backward_preprocess")
+                _backward_preprocess(s, P, M, (m, sh, None, op, sc, rot, None), radii, None, mine, grads, device)
+        d_m2, _, d_op, d_m3, _, d_sh, d_sc, d_rot = grads
         return (d_m3, d_m2 if ctx.has_means2D else None, d_sh, d_op.view(ctx.op_shape), d_sc, d_rot, None, None, None, None,
                 d_dc.view(ctx.dc_shape) if ctx.has_dc else None)
 
@@ -662,60 +627,35 @@ def route_plan_torch(miny: torch.Tensor, maxy: torch.Tensor, tiles: torch.Tensor
 
 
 def _i32_array(vals):
-    import ctypes as C
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
 def _i64_array(vals):
-    import ctypes as C
     return (C.c_int64 * len(vals))(*[int(v) for v in vals])
 
 
 def hip_preprocess_shard(raster_settings, means3D, sh, opacities, scales, rotations, dc=None):
     """gsr_preprocess_forward on this rank's shard: (records[P,16], radii[P], M, contiguous inputs)."""
-    import ctypes as C
-    from . import _lib, _sized, _f32c, _make_settings, _ptr, _stream_ptr, _require_cuda
-    lib = _lib.load()
-    _require_cuda(means3D, "means3D")
-    device = means3D.device
-    P = int(means3D.shape[0])
-    m_c, sh_c, op_c, sc_c, rot_c, dc_c = (_f32c(t) for t in (means3D, sh, opacities, scales, rotations, dc))
-    M = int(sh_c.shape[1]) + (1 if dc_c is not None else 0)
-    if dc_c is not None and (M != 16 or dc_c.data_ptr() % 16 or sh_c.data_ptr() % 16):
-        raise _lib.GsrError("sharded renderer: the split SH form needs degree-3 storage (dc[P,1,3] + shs[P,15,3])")
-    keep: list = []
-    with torch.cuda.device(device):
-        s = _make_settings(raster_settings, keep, None, False)
-        if dc_c is not None:
-            s.sh_dc = dc_c.data_ptr()
-        records = torch.empty(P, 16, dtype=torch.float32, device=device)
-        radii = torch.empty(P, dtype=torch.int32, device=device)
-        scratch = torch.empty(_sized("geom_shard", device, lib.gsr_geometry_bytes(P)), dtype=torch.uint8, device=device)
-        _lib.check(lib.gsr_preprocess_forward(C.byref(s), P, M, _ptr(m_c), _ptr(sh_c), None, _ptr(op_c), _ptr(sc_c),
-                                              _ptr(rot_c), None, _ptr(scratch), _ptr(radii), _ptr(records), _stream_ptr(device)),
-                   "gsr_preprocess_forward")
-    return records, radii, M, (m_c, sh_c, op_c, sc_c, rot_c, dc_c)
+    _, records, radii, M, inputs = _preprocess_shard(raster_settings, None, [], None, means3D, sh, opacities, scales, rotations, dc,
+                                                     "sharded renderer")
+    return records, radii, M, inputs
 
 
 def hip_route_count(records: torch.Tensor, bounds: Sequence[int]):
     """gsr_route_count: (counts int32[G] on the device, scratch) -- no host sync."""
-    import ctypes as C
-    from . import _lib, _ptr, _stream_ptr
     lib = _lib.load()
     device = records.device
     P, G = int(records.shape[0]), len(bounds) - 1
     with torch.cuda.device(device):
         scratch = torch.empty(max(128, lib.gsr_route_scratch_bytes(P, G)), dtype=torch.uint8, device=device)
         counts = torch.empty(G, dtype=torch.int32, device=device)
-        _lib.check(lib.gsr_route_count(P, _ptr(records), G, _i32_array(bounds), _ptr(scratch), _ptr(counts), _stream_ptr(device)),
+        _lib.check(lib.gsr_route_count(P, _ptr(records), G, _i32_array(bounds), _ptr(scratch), _ptr(counts), _pkg._stream_ptr(device)),
                    "gsr_route_count")
     return counts, scratch
 
 
 def hip_route_pack(records: torch.Tensor, bounds: Sequence[int], send_counts: Sequence[int], scratch: torch.Tensor):
     """gsr_route_pack: (packed[sum,12], send_ids int32[sum], offsets list of G+1)."""
-    import ctypes as C
-    from . import _lib, _ptr, _stream_ptr
     lib = _lib.load()
     device = records.device
     P, G = int(records.shape[0]), len(bounds) - 1
@@ -726,13 +666,12 @@ def hip_route_pack(records: torch.Tensor, bounds: Sequence[int], send_counts: Se
         packed = torch.empty(offsets[-1], PACKED_WORDS, dtype=torch.float32, device=device)
         send_ids = torch.empty(offsets[-1], dtype=torch.int32, device=device)
         _lib.check(lib.gsr_route_pack(P, _ptr(records), G, _i32_array(bounds), _i64_array(offsets), _ptr(scratch), _ptr(packed),
-                                      _ptr(send_ids), _stream_ptr(device)), "gsr_route_pack")
+                                      _ptr(send_ids), _pkg._stream_ptr(device)), "gsr_route_pack")
     return packed, send_ids, offsets
 
 
 def hip_route_pack_fixed(records: torch.Tensor, bounds: Sequence[int], capacity: int, scratch: torch.Tensor, counts: torch.Tensor):
     """gsr_route_pack_fixed: (segments[G * (capacity + 1), 12], send_ids int32[G * (capacity + 1)]) -- no host knowledge of the counts."""
-    from . import _lib, _ptr, _stream_ptr
     lib = _lib.load()
     device = records.device
     P, G = int(records.shape[0]), len(bounds) - 1
@@ -741,29 +680,17 @@ def hip_route_pack_fixed(records: torch.Tensor, bounds: Sequence[int], capacity:
         packed = torch.empty(rows, PACKED_WORDS, dtype=torch.float32, device=device)
         send_ids = torch.empty(rows, dtype=torch.int32, device=device)
         _lib.check(lib.gsr_route_pack_fixed(P, _ptr(records), G, _i32_array(bounds), int(capacity), _ptr(scratch), _ptr(counts),
-                                            _ptr(packed), _ptr(send_ids), _stream_ptr(device)), "gsr_route_pack_fixed")
+                                            _ptr(packed), _ptr(send_ids), _pkg._stream_ptr(device)), "gsr_route_pack_fixed")
     return packed, send_ids
 
 
 def hip_render_segments(raster_settings, band, segs: torch.Tensor, n_segments: int, capacity: int, no_backward: bool):
     """gsr_rasterize_from_segments on this rank's band (see hip_render_packed); the state's Gaussian count is
     n_segments * (capacity + 1)."""
-    import ctypes as C
-    from . import _lib, _Buffer, _make_settings, _ptr, _stream_ptr
-    lib = _lib.load()
-    device = segs.device
-    H, W = int(raster_settings.image_height), int(raster_settings.image_width)
     keep: list = []
-    with torch.cuda.device(device):
+    with torch.cuda.device(segs.device):
         s = _make_settings(raster_settings, keep, band, no_backward)
-        color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
-        invdepth = torch.zeros(1, H, W, dtype=torch.float32, device=device)
-        geom, binning, img = _Buffer(device, "geom"), _Buffer(device, "binning"), _Buffer(device, "image")
-        nr = C.c_int32(0)
-        _lib.check(lib.gsr_rasterize_from_segments(C.byref(s), int(n_segments), int(capacity), _ptr(segs), geom.cb, None, binning.cb,
-                                                   None, img.cb, None, _ptr(color), _ptr(invdepth), C.byref(nr), _stream_ptr(device)),
-                   "gsr_rasterize_from_segments")
-    return color, invdepth, (geom.t, binning.t, img.t, int(nr.value))
+        return _rasterize_records("gsr_rasterize_from_segments", s, (int(n_segments), int(capacity)), segs, segs.device)
 
 
 def _fixed_exchange_forward(records, bounds, counts, rscratch, policy: ExchangePolicy, group, async_op: bool = False):
@@ -786,22 +713,10 @@ def _fixed_exchange_forward(records, bounds, counts, rscratch, policy: ExchangeP
 def hip_render_packed(raster_settings, band, recv: torch.Tensor, no_backward: bool):
     """gsr_rasterize_from_packed on this rank's band: (color[3,H,W], invdepth[1,H,W], state) with only the band's rows
     written (zeros elsewhere); state = (geom, binning, img, num_rendered) for gsr_backward_blend."""
-    import ctypes as C
-    from . import _lib, _Buffer, _make_settings, _ptr, _stream_ptr
-    lib = _lib.load()
-    device = recv.device
-    H, W = int(raster_settings.image_height), int(raster_settings.image_width)
     keep: list = []
-    with torch.cuda.device(device):
+    with torch.cuda.device(recv.device):
         s = _make_settings(raster_settings, keep, band, no_backward)
-        color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
-        invdepth = torch.zeros(1, H, W, dtype=torch.float32, device=device)
-        geom, binning, img = _Buffer(device, "geom"), _Buffer(device, "binning"), _Buffer(device, "image")
-        nr = C.c_int32(0)
-        _lib.check(lib.gsr_rasterize_from_packed(C.byref(s), int(recv.shape[0]), _ptr(recv), geom.cb, None, binning.cb, None,
-                                                 img.cb, None, _ptr(color), _ptr(invdepth), C.byref(nr), _stream_ptr(device)),
-                   "gsr_rasterize_from_packed")
-    return color, invdepth, (geom.t, binning.t, img.t, int(nr.value))
+        return _rasterize_records("gsr_rasterize_from_packed", s, (int(recv.shape[0]),), recv, recv.device)
 
 
 class _GaussianShardedHip(torch.autograd.Function):
@@ -854,9 +769,6 @@ class _GaussianShardedHip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_radii, g_depth):
-        import ctypes as C
-        from . import _lib, _sized, _f32c, _make_settings, _ptr, _stream_ptr
-        lib = _lib.load()
         m, sh, op, sc, rot, radii, geom, binning, img, send_ids, dc = ctx.saved_tensors
         device = m.device
         P, P_recv, M = int(m.shape[0]), ctx.P_recv, ctx.M
@@ -864,27 +776,14 @@ class _GaussianShardedHip(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=device)
         if g_color is None:
             g_color = torch.zeros(3, int(rs.image_height), int(rs.image_width), **f)
-        d_m2, d_col, d_op = torch.empty(P, 3, **f), torch.empty(P, 3, **f), torch.empty(P, 1, **f)
-        d_m3, d_cov = torch.empty(P, 3, **f), torch.empty(P, 6, **f)
-        d_sh = torch.empty(P, M - 1 if ctx.has_dc else M, 3, **f)
-        d_dc = torch.empty(P, 1, 3, **f) if ctx.has_dc else None
-        d_sc, d_rot = torch.empty(P, 3, **f), torch.empty(P, 4, **f)
+        grads, d_dc = _gradients(P, device, True, True, M - 1 if ctx.has_dc else M, ctx.has_dc, True, True)
         keep: list = []
         with torch.cuda.device(device):
-            st = _stream_ptr(device)
             s = _make_settings(rs, keep, ctx.band)
             if ctx.has_dc:
                 s.sh_dc, s.dL_dsh_dc = dc.data_ptr(), d_dc.data_ptr()
             if P_recv > 0:
-                scratch = torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P_recv, ctx.num_rendered)),
-                                      dtype=torch.uint8, device=device)
-                rec_ptr = C.c_void_p(0)
-                gc = _f32c(g_color)
-                gd = _f32c(g_depth) if g_depth is not None else None
-                _lib.check(lib.gsr_backward_blend(C.byref(s), P_recv, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img),
-                                                  _ptr(gc), _ptr(gd), _ptr(scratch), C.byref(rec_ptr), st), "gsr_backward_blend")
-                off = int(rec_ptr.value) - scratch.data_ptr()
-                full = scratch[off:off + P_recv * 48].view(torch.float32).view(P_recv, 12)
+                full = _backward_blend(s, P_recv, _Forward(geom, binning, img, ctx.num_rendered), _f32c(g_color), _f32c(g_depth), device)
             else:
                 full = torch.empty(0, 12, **f)
             if ctx.fixed_capacity is not None:      # same layout back: block g of the gradient rows belongs to rank g
@@ -893,12 +792,10 @@ class _GaussianShardedHip(torch.autograd.Function):
                 returned, _ = all_to_all_rows(full, ctx.recv_counts, ctx.send_counts, ctx.group)      # rows back to their owners
             if P > 0:
                 mine = torch.empty(P, 12, **f)
-                _lib.check(lib.gsr_route_return(P, len(ctx.offsets) - 1, _i64_array(ctx.offsets), _ptr(send_ids), _ptr(returned),
-                                                _ptr(mine), st), "gsr_route_return")
-                _lib.check(lib.gsr_backward_preprocess(C.byref(s), P, M, _ptr(m), _ptr(sh), None, _ptr(op), _ptr(sc), _ptr(rot),
-                                                       None, _ptr(radii), None, _ptr(mine), _ptr(d_m2), _ptr(d_col), _ptr(d_op),
-                                                       _ptr(d_m3), _ptr(d_cov), _ptr(d_sh), _ptr(d_sc), _ptr(d_rot), st),
-                           "gsr_backward_preprocess")
+                _lib.check(_lib.load().gsr_route_return(P, len(ctx.offsets) - 1, _i64_array(ctx.offsets), _ptr(send_ids), _ptr(returned),
+                                                        _ptr(mine), _pkg._stream_ptr(device)), "gsr_route_return")
+                _backward_preprocess(s, P, M, (m, sh, None, op, sc, rot, None), radii, None, mine, grads, device)
+        d_m2, _, d_op, d_m3, _, d_sh, d_sc, d_rot = grads
         return (d_m3, d_m2 if ctx.has_means2D else None, d_sh, d_op.view(ctx.op_shape), d_sc, d_rot, None, None, None,
                 d_dc.view(ctx.dc_shape) if ctx.has_dc else None)
 

@@ -163,3 +163,50 @@ int main(void) {
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     assert "abi 4 ok" in out.stdout
+
+
+def test_signature_table_matches_the_header():
+    """_lib.SIGNATURES is the one place the package declares argument types: every entry has as many argument types as its prototype
+    in include/gsr.h has parameters."""
+    from diff_gaussian_rasterization import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsr.h")).read(), flags=re.S)
+    protos = {m.group(1): m.group(2).strip() for m in re.finditer(r"\b(gsr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)}
+    assert set(protos) == set(_lib.SIGNATURES), set(protos) ^ set(_lib.SIGNATURES)
+    for name, (_, argtypes) in _lib.SIGNATURES.items():
+        n = 0 if protos[name] in ("", "void") else protos[name].count(",") + 1
+        assert len(argtypes) == n, (name, len(argtypes), n)
+
+
+def test_abi_mismatch_binds_the_symbols_an_older_library_has(tmp_path, monkeypatch):
+    """A library of the current ABI version without the two camera-gradient symbols (a stub built with the host compiler): with
+    GSR_ALLOW_ABI_MISMATCH=1 the loader binds what it exports with the declared types; without it, it names what is missing."""
+    import subprocess
+    from unittest import mock
+    import simt_build
+    from diff_gaussian_rasterization import _lib
+    absent = ("gsr_camera_grad_scratch_bytes", "gsr_backward_preprocess_camera")
+    src = tmp_path / "stub.cpp"
+    src.write_text("".join(f'extern "C" int {n}(void) {{ return {_lib.ABI_VERSION if n == "gsr_abi_version" else 0}; }}\n'
+                           for n in _lib.EXPORTS if n not in absent))
+    so = tmp_path / "libgsr_stub.so"
+    subprocess.check_call([simt_build.CXX, "-shared", "-fPIC", str(src), "-o", str(so)])
+    real_cdll = _lib.C.CDLL
+    monkeypatch.setenv("GSR_LIB", str(so))
+    monkeypatch.delenv("GSR_OPTIONS", raising=False)
+    # (RTLD_LOCAL: the stub must not enter the process's global symbol scope, where a product library loaded later would bind to it)
+    with mock.patch.object(_lib.C, "CDLL", lambda p, mode=0: real_cdll(p)):
+        monkeypatch.setattr(_lib, "_lib", None)
+        monkeypatch.setenv("GSR_ALLOW_ABI_MISMATCH", "1")
+        lib = _lib.load()
+        assert lib._name == str(so)
+        for name, (restype, argtypes) in _lib.SIGNATURES.items():
+            if name in absent:
+                assert not hasattr(lib, name), name
+            else:
+                fn = getattr(lib, name)
+                assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
+        monkeypatch.setattr(_lib, "_lib", None)
+        monkeypatch.delenv("GSR_ALLOW_ABI_MISMATCH")
+        with pytest.raises(_lib.GsrError, match="does not export") as err:
+            _lib.load()
+        assert all(n in str(err.value) for n in absent), str(err.value)
