@@ -633,7 +633,7 @@ static bool use_bucket_sort(int P, int dev_id) {
 // `seq` is the sequence number that kernel's last workgroup publishes with R.
 static int bin_and_render(const GsrRasterSettings* settings, const GsrCamDev& cam, int P, GsrGeom& g, HostWordLease& lease, uint32_t seq,
                           int n_range /*workgroups of the key-producing kernel*/, GsrResizeFn binning_resize, void* binning_user, GsrResizeFn image_resize, void* image_user,
-                          float* out_color, float* out_invdepth, int32_t* num_rendered, hipStream_t st) {
+                          float* out_color, float* out_invdepth, int32_t* num_rendered, hipStream_t st, const GsrCompositeDev* comp = nullptr) {
     const int dev_id = lease.dev;
     HostWord& hw_slot = lease.hw;
     const int order_buf = depth_order_buffer_index();
@@ -753,7 +753,7 @@ static int bin_and_render(const GsrRasterSettings* settings, const GsrCamDev& ca
     {   StageTimer t(GSR_STAGE_RENDER, st);
         gsr_launch_render_forward(cam, im.ranges, b.vals[list_buf], g.splats, settings->no_backward ? nullptr : im.final_T,
                                   settings->no_backward ? nullptr : im.n_contrib, settings->no_backward ? nullptr : im.block_steps,
-                                  out_color, out_invdepth, g_render_fwd_variant, g_count_on ? counters_for_current_device() : nullptr, st);
+                                  out_color, out_invdepth, g_render_fwd_variant, g_count_on ? counters_for_current_device() : nullptr, st, 0, -1, comp);
     }
     STAGE_CHECK("render");
     HIP_OK(hipGetLastError());
@@ -761,12 +761,17 @@ static int bin_and_render(const GsrRasterSettings* settings, const GsrCamDev& ca
 }
 
 
-int gsr_rasterize_forward(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
-                          const float* colors_precomp, const float* opacities, const float* scales,
-                          const float* rotations, const float* cov3D_precomp, GsrResizeFn geom_resize, void* geom_user,
-                          GsrResizeFn binning_resize, void* binning_user, GsrResizeFn image_resize, void* image_user,
-                          float* out_color, float* out_invdepth, int32_t* radii, int32_t* num_rendered, void* stream) {
+// gsr_rasterize_forward and, with `extra`, gsr_rasterize_forward_composite
+static int rasterize_forward(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                             const float* colors_precomp, const float* opacities, const float* scales,
+                             const float* rotations, const float* cov3D_precomp, GsrResizeFn geom_resize, void* geom_user,
+                             GsrResizeFn binning_resize, void* binning_user, GsrResizeFn image_resize, void* image_user,
+                             float* out_color, float* out_invdepth, int32_t* radii, int32_t* num_rendered, const GsrCompositeOut* extra,
+                             void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    GsrCompositeDev comp{nullptr, nullptr, nullptr};
+    if (extra) { comp.out_alpha = extra->out_alpha; comp.bg_image = extra->bg_image; }
+    const bool composite = extra != nullptr;      // (P == 0: the composite call blends the background, see below)
     GsrCamDev cam;
     int rc = make_cam(settings, M, cam);
     if (rc != GSR_OK) return rc;
@@ -777,6 +782,21 @@ int gsr_rasterize_forward(const GsrRasterSettings* settings, int P, int M, const
     if (!out_color || !num_rendered) return fail(GSR_ERR_INVALID_ARG, "out_color / num_rendered are NULL");
     const size_t npix = (size_t)cam.W * cam.H;
     *num_rendered = 0;
+    if (P == 0 && composite) {
+        // the composite contract: alpha = 0 and color = B in the band (zeros outside it) -- the blend over empty tile ranges, inference
+        // build: no state is kept, the composite backward needs none for P == 0
+        if (!image_resize) return fail(GSR_ERR_INVALID_ARG, "resize callbacks are NULL");
+        char* ibase = (char*)image_resize(image_user, gsr_image_bytes(cam.W, cam.H));
+        if (!ibase) return fail(GSR_ERR_ALLOC, "image buffer resize returned NULL");
+        GsrImage im = gsr_carve_image(ibase, cam.W, cam.H);
+        HIP_OK(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * (size_t)cam.gx * cam.gy, st));
+        HIP_OK(hipMemsetAsync(out_color, 0, npix * 3 * sizeof(float), st));
+        if (out_invdepth) HIP_OK(hipMemsetAsync(out_invdepth, 0, npix * sizeof(float), st));
+        if (comp.out_alpha) HIP_OK(hipMemsetAsync(comp.out_alpha, 0, npix * sizeof(float), st));
+        gsr_launch_render_forward(cam, im.ranges, nullptr, nullptr, nullptr, nullptr, nullptr, out_color, out_invdepth, 0, nullptr, st, 0, -1, &comp);
+        HIP_OK(hipGetLastError());
+        return GSR_OK;
+    }
     if (P == 0) {   // reference behaviour: zero image (not background), nothing else touched
         HIP_OK(hipMemsetAsync(out_color, 0, npix * 3 * sizeof(float), st));
         if (out_invdepth) HIP_OK(hipMemsetAsync(out_invdepth, 0, npix * sizeof(float), st));
@@ -799,7 +819,27 @@ int gsr_rasterize_forward(const GsrRasterSettings* settings, int P, int M, const
     }
     STAGE_CHECK("preprocess");
     return bin_and_render(settings, cam, P, g, lease, seq, n_range, binning_resize, binning_user, image_resize, image_user, out_color, out_invdepth,
-                          num_rendered, st);
+                          num_rendered, st, (comp.out_alpha || comp.bg_image) ? &comp : nullptr);
+}
+
+int gsr_rasterize_forward(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                          const float* colors_precomp, const float* opacities, const float* scales,
+                          const float* rotations, const float* cov3D_precomp, GsrResizeFn geom_resize, void* geom_user,
+                          GsrResizeFn binning_resize, void* binning_user, GsrResizeFn image_resize, void* image_user,
+                          float* out_color, float* out_invdepth, int32_t* radii, int32_t* num_rendered, void* stream) {
+    return rasterize_forward(settings, P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, geom_resize, geom_user,
+                             binning_resize, binning_user, image_resize, image_user, out_color, out_invdepth, radii, num_rendered, nullptr, stream);
+}
+
+int gsr_rasterize_forward_composite(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
+                                    const float* colors_precomp, const float* opacities, const float* scales,
+                                    const float* rotations, const float* cov3D_precomp, GsrResizeFn geom_resize, void* geom_user,
+                                    GsrResizeFn binning_resize, void* binning_user, GsrResizeFn image_resize, void* image_user,
+                                    float* out_color, float* out_invdepth, int32_t* radii, int32_t* num_rendered,
+                                    const GsrCompositeOut* extra, void* stream) {
+    if (!extra) return fail(GSR_ERR_INVALID_ARG, "extra (GsrCompositeOut) is NULL");
+    return rasterize_forward(settings, P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, geom_resize, geom_user,
+                             binning_resize, binning_user, image_resize, image_user, out_color, out_invdepth, radii, num_rendered, extra, stream);
 }
 
 int gsr_preprocess_forward(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
@@ -1004,17 +1044,44 @@ static int list_buffer_index(int n_tiles) {
     return gsr_sort_plan(bits_for((uint32_t)n_tiles), GSR_TILE_DIGIT_BITS, pb) & 1;
 }
 
-int gsr_backward_blend(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
-                       const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
-                       const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out, void* stream) {
+size_t gsr_composite_grad_scratch_bytes(int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    return gsr_bg_grad_blocks((int64_t)width * height) * 3 * sizeof(double);
+}
+
+// gsr_backward_blend and, with `extra`, gsr_backward_blend_composite
+static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                          const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                          const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out, const GsrCompositeGrads* extra,
+                          void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GsrCamDev cam;
     int rc = make_cam(settings, 0, cam);
     if (rc != GSR_OK) return rc;
     if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
-    if (P == 0) return GSR_OK;
+    GsrCompositeDev comp{nullptr, nullptr, nullptr};
+    const bool bg_grad = extra && (extra->dL_dbg_image || extra->dL_dbg);
+    if (extra) {
+        comp.bg_image = extra->bg_image;
+        comp.dL_dalpha = extra->dL_dout_alpha;
+        if (extra->dL_dbg && !extra->scratch) return fail(GSR_ERR_INVALID_ARG, "dL_dbg needs scratch (gsr_composite_grad_scratch_bytes)");
+        if (((uintptr_t)extra->scratch) & 7) return fail(GSR_ERR_INVALID_ARG, "composite gradient scratch must be 8-byte aligned");
+        if (bg_grad && (!dL_dout_color || (P > 0 && !image_buffer)))
+            return fail(GSR_ERR_INVALID_ARG, "dL_dbg_image / dL_dbg need dL_dout_color and the image buffer");
+    }
+    if (bg_grad) {
+        // every pixel of the band, also those no Gaussian reaches; P == 0: the forward kept no state and T_final = 1 everywhere
+        const float* final_T = P > 0 ? gsr_carve_image((char*)image_buffer, cam.W, cam.H).final_T : nullptr;
+        const int row0 = cam.tile_y0 * GSR_TILE < cam.H ? cam.tile_y0 * GSR_TILE : cam.H;
+        const int row1 = cam.tile_y1 * GSR_TILE < cam.H ? cam.tile_y1 * GSR_TILE : cam.H;
+        StageTimer t(GSR_STAGE_RENDER_BWD, st);
+        gsr_launch_bg_grad((int64_t)cam.W * cam.H, cam.W, row0, row1, final_T, dL_dout_color, extra->dL_dbg_image, extra->dL_dbg,
+                           (double*)extra->scratch, st);
+    }
+    if (P == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
     if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout_color || !bwd_scratch)
         return fail(GSR_ERR_INVALID_ARG, "state buffers / dL_dout_color / bwd_scratch are NULL");
+    const GsrCompositeDev* compp = (comp.bg_image || comp.dL_dalpha) ? &comp : nullptr;
     GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
     GsrBinning b = gsr_carve_binning((char*)binning_buffer, num_rendered);
     GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
@@ -1030,10 +1097,10 @@ int gsr_backward_blend(const GsrRasterSettings* settings, int P, int32_t num_ren
                                            dL_dout_color, dL_dout_invdepth, sg, nullptr, nullptr, num_rendered, 1, 0, nullptr, st);
         } else {
             // (the flag words of the instances are cleared by the launcher: in the plan kernel's launch, or with a fill)
-            gsr_launch_render_backward(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
+            gsr_launch_render_backward_composite(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
                                        g_bwd_heavy_first ? im.tile_order : nullptr,
                                        dL_dout_color, dL_dout_invdepth, nullptr, w.inst_grads, w.inst_flag, num_rendered,
-                                       g_render_bwd_variant, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st);
+                                       g_render_bwd_variant, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st, compp);
         }
     }
     STAGE_CHECK("render backward blend");
@@ -1045,6 +1112,22 @@ int gsr_backward_blend(const GsrRasterSettings* settings, int P, int32_t num_ren
     STAGE_CHECK("render backward reduce");
     HIP_OK(hipGetLastError());
     return GSR_OK;
+}
+
+int gsr_backward_blend(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                       const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                       const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out, void* stream) {
+    return backward_blend(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, dL_dout_color, dL_dout_invdepth, bwd_scratch,
+                          splat_grads_out, nullptr, stream);
+}
+
+int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                                 const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                                 const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out,
+                                 const GsrCompositeGrads* extra, void* stream) {
+    if (!extra) return fail(GSR_ERR_INVALID_ARG, "extra (GsrCompositeGrads) is NULL");
+    return backward_blend(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, dL_dout_color, dL_dout_invdepth, bwd_scratch,
+                          splat_grads_out, extra, stream);
 }
 
 // gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera

@@ -265,11 +265,19 @@ __device__ __forceinline__ void gsr_trace_wave(unsigned long long* counters, uns
 }
 #endif
 
+// optional inputs / outputs of the two blend kernels beyond the reference's contract (gsr_rasterize_forward_composite /
+// gsr_backward_blend_composite): every pointer may be NULL, and all NULL is the plain call
+struct GsrCompositeDev {
+    float* out_alpha;            // forward: [H*W] 1 - final_T
+    const float* bg_image;       // both: [3,H*W] per-pixel background instead of cam.bg
+    const float* dL_dalpha;      // backward: [H*W] gradient of the alpha image
+};
 void gsr_launch_render_forward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
                                const float4* splats, float* final_T, uint32_t* n_contrib, uint32_t* block_steps /*NULL unless tracking*/,
                                float* out_color, float* out_invdepth, int variant,
                                unsigned long long* counters /*NULL or [4] work counters*/, hipStream_t st,
-                               int tile_off = 0, int tile_cnt = -1 /*the launch blends tiles [tile_off, tile_off + tile_cnt) of the band (multiple of 8; -1 = all)*/);
+                               int tile_off = 0, int tile_cnt = -1 /*the launch blends tiles [tile_off, tile_off + tile_cnt) of the band (multiple of 8; -1 = all)*/,
+                               const GsrCompositeDev* comp = nullptr);
 void gsr_set_render_fwd_lds_pad(int bytes);      // render_fwd.hip (tuning option render_fwd_lds_pad)
 // variant: 0 = default (independent quadrant waves); 1 (global atomics) and 4 (round 1's workgroup-per-tile kernel) exist
 // only in builds with -DGSR_AB_VARIANTS
@@ -282,6 +290,18 @@ void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const
                                 float* inst_grads /*[4][R,12]*/, uint32_t* inst_flag /*[R]*/, int64_t R, int variant,
                                 int order_mode /*plan kernel: 1 tiles by the sum of their blocks, 2 tiles by their heaviest half, 3 half tiles (waves)*/,
                                 unsigned long long* counters, hipStream_t st);
+// the same with the optional per-pixel background / alpha-image gradient of gsr_backward_blend_composite (comp may be NULL: the plain call)
+void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                                          const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                                          const uint32_t* block_steps, uint32_t* tile_order, const float* dL_dpix, const float* dL_dinvdepth,
+                                          float* splat_grads, float* inst_grads, uint32_t* inst_flag, int64_t R, int variant, int order_mode,
+                                          unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp);
+// background gradient (render_bwd.hip): dL_dbg_image[c][p] = T(p) * dL_dpix[c][p] and / or dL_dbg[c] = sum over p, with T = final_T inside the
+// band's pixel rows [row0, row1) (1 where final_T is NULL: no Gaussian at all) and 0 outside.  partials: gsr_bg_grad_blocks(W * H) * 3 doubles.
+#define GSR_BG_GRAD_PIXELS 2048      // pixels per workgroup (256 threads x 8)
+static inline size_t gsr_bg_grad_blocks(int64_t npix) { return (size_t)((npix + GSR_BG_GRAD_PIXELS - 1) / GSR_BG_GRAD_PIXELS); }
+void gsr_launch_bg_grad(int64_t npix, int W, int row0, int row1, const float* final_T, const float* dL_dpix, float* dL_dbg_image,
+                        float* dL_dbg, double* partials, hipStream_t st);
 size_t gsr_reduce_units(int64_t R);      // units of 1024 instance records the reduce works in
 void gsr_launch_reduce_instances(int P, int64_t R, const uint32_t* order, const uint32_t* offsets, const float4* splats,
                                  const float* inst_grads, const uint32_t* inst_flag, float* splat_grads, uint2* unit_first,

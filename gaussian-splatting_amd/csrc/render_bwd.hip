@@ -270,7 +270,8 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
                 const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
                 const float* __restrict__ dL_dinvdepth, float4* __restrict__ slot_grads /*[4][R] records of 3 float4*/,
                 uint8_t* __restrict__ slot_flags /*[R][4]*/, int64_t R, const uint32_t* __restrict__ tile_order /*NULL: index order*/,
-                int wave_order /*tile_order lists (tile << 1 | half) per WAVE, heaviest first*/, unsigned long long* __restrict__ counters) {
+                int wave_order /*tile_order lists (tile << 1 | half) per WAVE, heaviest first*/, unsigned long long* __restrict__ counters,
+                GsrCompositeDev comp /*optional per-pixel background / alpha-image gradient: read in the prologue only*/) {
     __shared__ float4 s_rec[64 * REC_STRIDE];
     __shared__ float s_grad[64 * 12];
     // the two halves of a tile get workgroup ids b and b + 16 -> same XCD -> they share the gathered records in L2;
@@ -319,7 +320,22 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
     const v2f dLb = {inA ? dL_dpix[2 * HW + pixA] : 0.f, inB ? dL_dpix[2 * HW + pixB] : 0.f};
     v2f dLd = {0.f, 0.f};
     if (HAS_DEPTH) dLd = (v2f){inA ? dL_dinvdepth[pixA] : 0.f, inB ? dL_dinvdepth[pixB] : 0.f};
-    const v2f Tf_bg = -T_final * (cam.bg[0] * dLr + cam.bg[1] * dLg + cam.bg[2] * dLb);
+    // Tf_bg = -T_final * (<B, dL/dpix> - dL/dalpha_image): the pixel-constant through which everything that depends on T_final alone -- the
+    // background term of the colour and the alpha image 1 - T_final -- reaches dL/dalpha_i.  The plain call keeps its expression.
+    v2f Tf_bg;
+    if (comp.bg_image == nullptr && comp.dL_dalpha == nullptr) {
+        Tf_bg = -T_final * (cam.bg[0] * dLr + cam.bg[1] * dLg + cam.bg[2] * dLb);
+    } else {
+        v2f B0 = {cam.bg[0], cam.bg[0]}, B1 = {cam.bg[1], cam.bg[1]}, B2 = {cam.bg[2], cam.bg[2]};
+        if (comp.bg_image) {
+            B0 = (v2f){inA ? comp.bg_image[pixA] : 0.f, inB ? comp.bg_image[pixB] : 0.f};
+            B1 = (v2f){inA ? comp.bg_image[HW + pixA] : 0.f, inB ? comp.bg_image[HW + pixB] : 0.f};
+            B2 = (v2f){inA ? comp.bg_image[2 * HW + pixA] : 0.f, inB ? comp.bg_image[2 * HW + pixB] : 0.f};
+        }
+        v2f dot = B0 * dLr + B1 * dLg + B2 * dLb;
+        if (comp.dL_dalpha) dot = dot - (v2f){inA ? comp.dL_dalpha[pixA] : 0.f, inB ? comp.dL_dalpha[pixB] : 0.f};
+        Tf_bg = -T_final * dot;
+    }
     uint32_t mxA = lastA, mxB = lastB;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -811,7 +827,93 @@ bwd_plan_kernel(int tile0, int n_band_tiles, const uint4* __restrict__ block_ste
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gradient of the background (gsr_backward_blend_composite): dL/dB[c][p] = T_final(p) dL/dC[c][p] at EVERY pixel of the band -- also where
+// no Gaussian contributes (T_final = 1) and in tiles the walk kernel is never launched for or returns early from, which is why this is
+// a kernel of its own and not an epilogue of the walk.  Workgroup b owns pixels [b * 2048, (b + 1) * 2048): thread t takes pixels
+// b * 2048 + k * 256 + t, k = 0..7 (coalesced), writes the three fp32 products of each and adds their exact fp64 values in k order; the 256
+// thread sums are added in LDS by a fixed tree.  bg_grad_finish adds the per-workgroup sums in a fixed order and rounds once to fp32.
+// No atomics, every output overwritten: two runs give the same bits.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+bg_grad_kernel(int64_t npix, int W, int row0, int row1, const float* __restrict__ final_T /*NULL: T = 1*/, const float* __restrict__ dL_dpix,
+               float* __restrict__ dL_dbg_image /*[3][npix] or NULL*/, double* __restrict__ partials /*[3][gridDim.x] or NULL*/) {
+    __shared__ double red[3][256];
+    const int t = threadIdx.x;
+    const int64_t lo = (int64_t)row0 * W, hi = (int64_t)row1 * W;      // the band's pixels
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+    float T[8], g0[8], g1[8], g2[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {      // all loads of the thread up front
+        const int64_t p = (int64_t)blockIdx.x * GSR_BG_GRAD_PIXELS + k * 256 + t;
+        const bool in = p < npix && p >= lo && p < hi;
+        const int64_t q = in ? p : 0;
+        T[k] = in ? (final_T ? final_T[q] : 1.0f) : 0.0f;
+        g0[k] = in ? dL_dpix[q] : 0.0f;
+        g1[k] = in ? dL_dpix[npix + q] : 0.0f;
+        g2[k] = in ? dL_dpix[2 * npix + q] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int64_t p = (int64_t)blockIdx.x * GSR_BG_GRAD_PIXELS + k * 256 + t;
+        if (p >= npix) continue;
+        if (dL_dbg_image) {
+            dL_dbg_image[p] = T[k] * g0[k];
+            dL_dbg_image[npix + p] = T[k] * g1[k];
+            dL_dbg_image[2 * npix + p] = T[k] * g2[k];
+        }
+        acc0 += (double)T[k] * (double)g0[k];
+        acc1 += (double)T[k] * (double)g1[k];
+        acc2 += (double)T[k] * (double)g2[k];
+    }
+    if (partials == nullptr) return;
+    red[0][t] = acc0; red[1][t] = acc1; red[2][t] = acc2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+            red[0][t] += red[0][t + w];
+            red[1][t] += red[1][t + w];
+            red[2][t] += red[2][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < 3) partials[(int64_t)t * gridDim.x + blockIdx.x] = red[t][0];
+}
+
+// one workgroup: dL_dbg[c] = sum of partials[c][0 .. rows): thread t adds rows t, t + 256, ... in that order, then the same tree
+__global__ void __launch_bounds__(256)
+bg_grad_finish(const double* __restrict__ partials, int rows, float* __restrict__ dL_dbg) {
+    __shared__ double red[3][256];
+    const int t = threadIdx.x;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int r = t; r < rows; r += 256) {
+        s0 += partials[r];
+        s1 += partials[(int64_t)rows + r];
+        s2 += partials[2 * (int64_t)rows + r];
+    }
+    red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+            red[0][t] += red[0][t + w];
+            red[1][t] += red[1][t + w];
+            red[2][t] += red[2][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < 3) dL_dbg[t] = (float)red[t][0];
+}
+
 }  // namespace
+
+void gsr_launch_bg_grad(int64_t npix, int W, int row0, int row1, const float* final_T, const float* dL_dpix, float* dL_dbg_image,
+                        float* dL_dbg, double* partials, hipStream_t st) {
+    const int blocks = (int)gsr_bg_grad_blocks(npix);
+    if (blocks <= 0) return;
+    hipLaunchKernelGGL(bg_grad_kernel, dim3(blocks), dim3(256), 0, st, npix, W, row0, row1, final_T, dL_dpix, dL_dbg_image,
+                       dL_dbg ? partials : nullptr);
+    if (dL_dbg) hipLaunchKernelGGL(bg_grad_finish, dim3(1), dim3(256), 0, st, (const double*)partials, blocks, dL_dbg);
+}
 
 int gsr_render_backward_variant_available(int variant) {
 #ifdef GSR_AB_VARIANTS
@@ -821,11 +923,15 @@ int gsr_render_backward_variant_available(int variant) {
 #endif
 }
 
-void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
-                                const float4* splats, const float* final_T, const uint32_t* n_contrib,
-                                const uint32_t* block_steps, uint32_t* tile_order,
-                                const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
-                                uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st) {
+namespace {
+// body of the two launchers below (comp_in may be NULL: the plain call)
+void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                            const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                            const uint32_t* block_steps, uint32_t* tile_order,
+                            const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
+                            uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st,
+                            const GsrCompositeDev* comp_in) {
+    const GsrCompositeDev comp = comp_in ? *comp_in : GsrCompositeDev{nullptr, nullptr, nullptr};
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0) return;
     const int groups = (n_band_tiles + 7) / 8;
@@ -866,11 +972,32 @@ void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const
     if (dL_dinvdepth)
         hipLaunchKernelGGL(render_bwd_half<true>, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats,
                            final_T, n_contrib, dL_dpix, dL_dinvdepth, reinterpret_cast<float4*>(inst_grads),
-                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters);
+                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters, comp);
     else
         hipLaunchKernelGGL(render_bwd_half<false>, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats,
                            final_T, n_contrib, dL_dpix, dL_dinvdepth, reinterpret_cast<float4*>(inst_grads),
-                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters);
+                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters, comp);
+}
+
+}  // namespace
+
+void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                                const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                                const uint32_t* block_steps, uint32_t* tile_order,
+                                const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
+                                uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st) {
+    launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, splat_grads,
+                           inst_grads, inst_flag, R, variant, order_mode, counters, st, nullptr);
+}
+
+void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                                          const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                                          const uint32_t* block_steps, uint32_t* tile_order,
+                                          const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
+                                          uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st,
+                                          const GsrCompositeDev* comp) {
+    launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, splat_grads,
+                           inst_grads, inst_flag, R, variant, order_mode, counters, st, comp);
 }
 
 size_t gsr_reduce_units(int64_t R) { return (size_t)((R + RU - 1) / RU); }

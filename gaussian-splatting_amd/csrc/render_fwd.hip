@@ -116,7 +116,8 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
                    const uint32_t* __restrict__ point_list, const float4* __restrict__ splats,
                    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ block_steps,
                    float* __restrict__ out_color, float* __restrict__ out_invdepth,
-                   unsigned long long* __restrict__ counters /*NULL unless profiling*/) {
+                   unsigned long long* __restrict__ counters /*NULL unless profiling*/,
+                   GsrCompositeDev comp /*optional alpha output / per-pixel background: wave-uniform NULL tests in the epilogue only*/) {
     __shared__ float4 s_rec_all[USE_LDS ? WPB * 64 * 3 : 1];
     float4* s_rec = s_rec_all + (USE_LDS ? (threadIdx.x >> 6) * 64 * 3 : 0);
     int tile_local, quad;
@@ -250,10 +251,17 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
             final_T[pix] = s.T;
             n_contrib[pix] = s.last;
         }
-        out_color[pix] = s.C0 + s.T * cam.bg[0];
-        out_color[HW + pix] = s.C1 + s.T * cam.bg[1];
-        out_color[2 * HW + pix] = s.C2 + s.T * cam.bg[2];
+        if (comp.bg_image) {      // per-pixel background [3,H,W] (gsr_rasterize_forward_composite): three loads instead of cam.bg
+            out_color[pix] = s.C0 + s.T * comp.bg_image[pix];
+            out_color[HW + pix] = s.C1 + s.T * comp.bg_image[HW + pix];
+            out_color[2 * HW + pix] = s.C2 + s.T * comp.bg_image[2 * HW + pix];
+        } else {
+            out_color[pix] = s.C0 + s.T * cam.bg[0];
+            out_color[HW + pix] = s.C1 + s.T * cam.bg[1];
+            out_color[2 * HW + pix] = s.C2 + s.T * cam.bg[2];
+        }
         if (out_invdepth) out_invdepth[pix] = s.D;
+        if (comp.out_alpha) comp.out_alpha[pix] = 1.0f - s.T;      // accumulated opacity, both builds (s.T is frozen at termination)
     }
 }
 
@@ -280,7 +288,8 @@ int gsr_render_forward_variant_available(int variant) {
 void gsr_launch_render_forward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
                                const float4* splats, float* final_T, uint32_t* n_contrib, uint32_t* block_steps,
                                float* out_color, float* out_invdepth, int variant, unsigned long long* counters, hipStream_t st,
-                               int tile_off, int tile_cnt) {
+                               int tile_off, int tile_cnt, const GsrCompositeDev* comp_in) {
+    const GsrCompositeDev comp = comp_in ? *comp_in : GsrCompositeDev{nullptr, nullptr, nullptr};
     int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (tile_off < 0 || tile_cnt < 0) { tile_off = 0; tile_cnt = n_band_tiles; }      // the whole band in one launch
     if (tile_off + tile_cnt < n_band_tiles) n_band_tiles = tile_off + tile_cnt;
@@ -292,10 +301,10 @@ void gsr_launch_render_forward(const GsrCamDev& cam, const uint2* ranges, const 
     do {                                                                                                                          \
         if (track)                                                                                                                \
             hipLaunchKernelGGL((render_fwd_wave_bf<USE_LDS_, WPB_, true>), dim3(GRID_), dim3(BLOCK_), g_render_fwd_lds_pad, st, cam, tile_off, n_band_tiles,    \
-                               ranges, point_list, splats, final_T, n_contrib, block_steps, out_color, out_invdepth, counters);  \
+                               ranges, point_list, splats, final_T, n_contrib, block_steps, out_color, out_invdepth, counters, comp);  \
         else                                                                                                                      \
             hipLaunchKernelGGL((render_fwd_wave_bf<USE_LDS_, WPB_, false>), dim3(GRID_), dim3(BLOCK_), g_render_fwd_lds_pad, st, cam, tile_off, n_band_tiles,   \
-                               ranges, point_list, splats, final_T, n_contrib, block_steps, out_color, out_invdepth, counters);  \
+                               ranges, point_list, splats, final_T, n_contrib, block_steps, out_color, out_invdepth, counters, comp);  \
     } while (0)
 #ifdef GSR_AB_VARIANTS
     if (variant == 1) {

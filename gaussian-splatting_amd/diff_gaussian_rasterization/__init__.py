@@ -124,7 +124,13 @@ class _Buffer:
         return self._holder[0]
 
 
-def _make_settings(rs: GaussianRasterizationSettings, keep: list, tile_rows, no_backward: bool = False) -> GsrRasterSettings:
+def _make_settings(rs: GaussianRasterizationSettings, keep: list, tile_rows, no_backward: bool = False, bg_image: bool = False) -> GsrRasterSettings:
+    """`bg_image`: the caller hands rs.bg to the composite entry points as a per-pixel image [3,H,W] as well (the single-GPU autograd function);
+    everywhere else -- the multi-GPU renderers included -- the C ABI reads three floats, so any other shape than [3] is refused."""
+    H, W = int(rs.image_height), int(rs.image_width)
+    if tuple(rs.bg.shape) != (3,) and not (bg_image and tuple(rs.bg.shape) == (3, H, W)):
+        raise GsrError(f"raster_settings.bg must have shape [3]" + (f" or [3, {H}, {W}] (image_height, image_width)" if bg_image else
+                       " here (a per-pixel background [3,H,W] is supported by the single-GPU rasterizer only)") + f", got {list(rs.bg.shape)}")
     dev_t = [_f32c(rs.bg), _f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos)]
     keep.extend(dev_t)
     s = GsrRasterSettings()
@@ -172,15 +178,19 @@ class _Forward(NamedTuple):
     num_rendered: int
 
 
-def _rasterize_forward(s, P, M, inputs, color, invdepth, radii, device, kinds=("geom", "binning", "image")) -> _Forward:
-    """gsr_rasterize_forward.  inputs = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp); `kinds` are the
-    _Buffer kinds of the geometry, binning and image buffers."""
+def _rasterize_forward(s, P, M, inputs, color, invdepth, radii, device, kinds=("geom", "binning", "image"), extra=None) -> _Forward:
+    """gsr_rasterize_forward, or with a _lib.CompositeOut `extra` (alpha image, per-pixel background) gsr_rasterize_forward_composite.
+    inputs = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp); `kinds` are the _Buffer kinds of the geometry,
+    binning and image buffers."""
     lib = _lib.load()
     geom, binning, img = (_Buffer(device, k) for k in kinds)
     nr = C.c_int32(0)
-    _lib.check(lib.gsr_rasterize_forward(C.byref(s), P, M, *[_ptr(t) for t in inputs], geom.cb, None, binning.cb, None, img.cb, None,
-                                         _ptr(color), _ptr(invdepth), _ptr(radii), C.byref(nr), _stream_ptr(device)),
-               "gsr_rasterize_forward")
+    args = (C.byref(s), P, M, *[_ptr(t) for t in inputs], geom.cb, None, binning.cb, None, img.cb, None, _ptr(color), _ptr(invdepth),
+            _ptr(radii), C.byref(nr))
+    if extra is None:
+        _lib.check(lib.gsr_rasterize_forward(*args, _stream_ptr(device)), "gsr_rasterize_forward")
+    else:
+        _lib.check(lib.gsr_rasterize_forward_composite(*args, C.byref(extra), _stream_ptr(device)), "gsr_rasterize_forward_composite")
     return _Forward(geom.t, binning.t, img.t, int(nr.value))
 
 
@@ -237,13 +247,21 @@ def _backward_scratch(lib, P, num_rendered, device) -> torch.Tensor:
     return torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P, num_rendered)), dtype=torch.uint8, device=device)
 
 
-def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device) -> torch.Tensor:
-    """gsr_backward_blend -> the per-Gaussian 48-byte gradient records [P,12], a view into the backward scratch."""
+def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device, extra=None) -> Optional[torch.Tensor]:
+    """gsr_backward_blend, or with a _lib.CompositeGrads `extra` (alpha-image gradient, per-pixel background, background gradient)
+    gsr_backward_blend_composite -> the per-Gaussian 48-byte gradient records [P,12], a view into the backward scratch (None for P == 0,
+    where only the composite call has anything to write: the background gradient)."""
     lib = _lib.load()
     scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
     rec_ptr = C.c_void_p(0)
-    _lib.check(lib.gsr_backward_blend(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color),
-                                      _ptr(g_depth), _ptr(scratch), C.byref(rec_ptr), _stream_ptr(device)), "gsr_backward_blend")
+    args = (C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color), _ptr(g_depth), _ptr(scratch),
+            C.byref(rec_ptr))
+    if extra is None:
+        _lib.check(lib.gsr_backward_blend(*args, _stream_ptr(device)), "gsr_backward_blend")
+    else:
+        _lib.check(lib.gsr_backward_blend_composite(*args, C.byref(extra), _stream_ptr(device)), "gsr_backward_blend_composite")
+    if P == 0:
+        return None
     off = int(rec_ptr.value) - scratch.data_ptr()
     return scratch[off:off + P * 48].view(torch.float32).view(P, 12)
 
@@ -370,9 +388,9 @@ def fuse_sh_adam_into_backward(optimizer, dc_param, rest_param):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None):
-        # viewmatrix / projmatrix / campos: raster_settings' own tensors, passed again so that autograd sees them (camera gradients,
-        # gsr_backward_preprocess_camera).  The kernels read them from raster_settings.
+                raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None, bg=None, return_alpha=False):
+        # viewmatrix / projmatrix / campos / bg: raster_settings' own tensors, passed again so that autograd sees them (camera gradients,
+        # gsr_backward_preprocess_camera; background gradient, gsr_backward_blend_composite).  The kernels read them from raster_settings.
         _lib.load()      # (a missing library is reported before anything else)
         _require_cuda(means3D, "means3D")
         _trim_cache_if_pending()
@@ -399,24 +417,37 @@ class _RasterizeGaussians(torch.autograd.Function):
         M = int(sh_c.shape[1]) if sh_c is not None and sh_c.dim() == 3 else 0
         if dc_c is not None:
             M += 1
+        # background: [3] (the reference's form) or a per-pixel image [3,H,W]; either may require grad (passed again as `bg`)
+        bg_c = _f32c(raster_settings.bg)
+        ctx.bg_image = bg_c.dim() == 3      # (the shape itself is checked by _make_settings)
+        ctx.bg_grad = bool(len(ctx.needs_input_grad) > 15 and ctx.needs_input_grad[15])
+        if grad_sync is not None and (ctx.bg_image or ctx.bg_grad or return_alpha):
+            raise GsrError("the alpha image, a per-pixel background and the background gradient are not supported together with grad_sync "
+                           "(multi-GPU renderers): detach / broadcast the background and call without return_alpha")
+        # the composite entry point only when something beyond the reference's contract is asked for
+        composite = bool(return_alpha) or ctx.bg_image or ctx.bg_grad
         keep: list = []
         with torch.cuda.device(device):
             # inside autograd.Function.forward grad mode is off; needs_input_grad tells whether a backward can follow
             ctx.camera_grad = any(ctx.needs_input_grad[12:15])
-            no_backward = not (any(ctx.needs_input_grad[:8]) or ctx.needs_input_grad[11] or ctx.camera_grad)
-            s = _make_settings(raster_settings, keep, tile_rows, no_backward)
+            no_backward = not (any(ctx.needs_input_grad[:8]) or ctx.needs_input_grad[11] or ctx.camera_grad or ctx.bg_grad)
+            s = _make_settings(raster_settings, keep, tile_rows, no_backward, bg_image=grad_sync is None)
             if dc_c is not None:
                 s.sh_dc = dc_c.data_ptr()
             color = torch.empty(3, H, W, dtype=torch.float32, device=device)
             invdepth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+            alpha = torch.empty(1, H, W, dtype=torch.float32, device=device) if return_alpha else None
             if tile_rows is not None:   # rows outside the band are not written by the kernels
                 color.zero_()
                 invdepth.zero_()
+                if alpha is not None:
+                    alpha.zero_()
+            extra = _lib.CompositeOut(alpha.data_ptr() if alpha is not None else None, bg_c.data_ptr() if ctx.bg_image else None) if composite else None
             radii = torch.empty(P, dtype=torch.int32, device=device)
             cpu_args = _cpu_copy((means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                   raster_settings)) if raster_settings.debug else None
             try:
-                fwd = _rasterize_forward(s, P, M, (means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c), color, invdepth, radii, device)
+                fwd = _rasterize_forward(s, P, M, (means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c), color, invdepth, radii, device, extra=extra)
             except Exception:
                 if cpu_args is not None:
                     torch.save(cpu_args, "snapshot_fw.dump")
@@ -444,6 +475,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise GsrError("camera gradients (viewmatrix / projmatrix / campos requiring grad) cannot be combined with the SH Adam step "
                            "fused into the backward (fuse_sh_adam_into_backward): remove the fusion or detach the camera tensors")
         ctx.cam_meta = tuple((t.shape, t.dtype) if t is not None else None for t in (viewmatrix, projmatrix, campos))
+        ctx.bg_meta = (bg.shape, bg.dtype) if bg is not None else None
+        ctx.return_alpha = bool(return_alpha)
         ctx.sh_given = sh is not None
         ctx.dc_shape = tuple(dc.shape) if dc is not None else None
         ctx.save_for_backward(means3D_c, sh_c if sh_c is not None else means3D_c.new_empty(0),
@@ -452,19 +485,22 @@ class _RasterizeGaussians(torch.autograd.Function):
                               rot_c if rot_c is not None else means3D_c.new_empty(0),
                               cov_c if cov_c is not None else means3D_c.new_empty(0),
                               radii, fwd.geom, fwd.binning, fwd.img,
-                              dc_c if dc_c is not None else means3D_c.new_empty(0))
+                              dc_c if dc_c is not None else means3D_c.new_empty(0),
+                              bg_c if ctx.bg_image else means3D_c.new_empty(0))
         ctx.mark_non_differentiable(radii)
         # an output nobody differentiates through (the inverse-depth image unless depth supervision is on, train.py:130-137)
         # arrives in backward as None instead of a materialised zero image: the blend backward then runs its build without
         # the 1/depth terms ("skip the invdepth terms when it is all-zero / None")
         ctx.set_materialize_grads(False)
+        if return_alpha:
+            return color, radii, invdepth, alpha
         return color, radii, invdepth
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_out_depth):
+    def backward(ctx, grad_out_color, grad_radii, grad_out_depth, grad_out_alpha=None):
         lib = _lib.load()
-        (means3D, sh, col, op, sc, rot, cov, radii, geom, binning, img, dc) = ctx.saved_tensors
-        if grad_out_color is None:          # only the inverse-depth image was used
+        (means3D, sh, col, op, sc, rot, cov, radii, geom, binning, img, dc, bg_img) = ctx.saved_tensors
+        if grad_out_color is None:          # only the inverse-depth and / or the alpha image was used
             rs_ = ctx.raster_settings
             grad_out_color = torch.zeros(3, int(rs_.image_height), int(rs_.image_width), dtype=torch.float32, device=means3D.device)
         has_sh, has_col, has_sc, has_rot, has_cov = ctx.flags
@@ -481,12 +517,27 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.camera_grad:      # [16] view, [16] projection, [3] campos (64-byte offsets), fp32
             cam_out = torch.zeros(48, dtype=torch.float32, device=device)
             cam_scratch = torch.empty(max(int(lib.gsr_camera_grad_scratch_bytes(P)), 8), dtype=torch.uint8, device=device)
-        if P > 0:
-            g_color = _f32c(grad_out_color)
-            g_depth = _f32c(grad_out_depth)
-            keep: list = []
+        # the composite blend backward only when the loss reaches the alpha image, the background is per pixel or its gradient is wanted:
+        # a colour / depth loss over a constant background runs what it ran before return_alpha existed
+        comp = dL_dbg = g_alpha = comp_scratch = None
+        if grad_out_alpha is not None or ctx.bg_image or ctx.bg_grad:
+            H, W = int(rs.image_height), int(rs.image_width)
+            g_alpha = _f32c(grad_out_alpha)
+            if ctx.bg_grad:      # [3,H,W] products, or their sums [3] with the reduction's scratch
+                dL_dbg = torch.empty((3, H, W) if ctx.bg_image else (3,), dtype=torch.float32, device=device)
+                if not ctx.bg_image:
+                    comp_scratch = torch.empty(max(int(lib.gsr_composite_grad_scratch_bytes(W, H)), 8), dtype=torch.uint8, device=device)
+            comp = _lib.CompositeGrads(_ptr(g_alpha), _ptr(bg_img) if ctx.bg_image else None,
+                                       _ptr(dL_dbg) if ctx.bg_image else None, None if ctx.bg_image else _ptr(dL_dbg), _ptr(comp_scratch))
+        g_color = _f32c(grad_out_color)
+        keep: list = []
+        if P == 0 and ctx.bg_grad:      # no Gaussian: T_final = 1 everywhere, the forward kept no state
             with torch.cuda.device(device):
-                s = _make_settings(rs, keep, ctx.tile_rows)
+                _backward_blend(_make_settings(rs, keep, ctx.tile_rows, bg_image=True), 0, _Forward(None, None, None, 0), g_color, None, device, comp)
+        if P > 0:
+            g_depth = _f32c(grad_out_depth)
+            with torch.cuda.device(device):
+                s = _make_settings(rs, keep, ctx.tile_rows, bg_image=ctx.bg_image)
                 if has_dc:
                     s.sh_dc = dc.data_ptr()
                     s.dL_dsh_dc = dL_ddc.data_ptr() if dL_ddc is not None else None
@@ -495,12 +546,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                 fwd = _Forward(geom, binning, img, ctx.num_rendered)
                 cpu_args = _cpu_copy((means3D, radii, col, sc, rot, cov, sh, grad_out_color, rs)) if rs.debug else None
                 try:
-                    if fused_adam is None and not ctx.camera_grad and ctx.grad_sync is None:
+                    if fused_adam is None and not ctx.camera_grad and ctx.grad_sync is None and comp is None:
                         _rasterize_backward(s, P, M, inputs, radii, fwd, g_color, g_depth, grads, device)
                     else:
                         # blend backward -> (multi-GPU: sum of the 48-byte per-Gaussian records across ranks, parallel.py) -> the
                         # per-Gaussian backward that also sums the camera gradient, or steps the two SH tensors in place
-                        records = _backward_blend(s, P, fwd, g_color, g_depth, device)
+                        records = _backward_blend(s, P, fwd, g_color, g_depth, device, comp)
                         if ctx.grad_sync is not None:
                             ctx.grad_sync(records)
                         if fused_adam is not None:
@@ -531,8 +582,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             cam_grads = tuple(None if (meta is None or not ctx.needs_input_grad[12 + k]) else
                               cam_out[16 * k:16 * k + (3 if k == 2 else 16)].reshape(meta[0]).to(meta[1])
                               for k, meta in enumerate(ctx.cam_meta))
+        if dL_dbg is not None:
+            dL_dbg = dL_dbg.reshape(ctx.bg_meta[0]).to(ctx.bg_meta[1])
         return (dL_dmeans3D, dL_dmeans2D if ctx.has_means2D else None, dL_dsh, dL_dcolors if has_col else None, dL_dopacity, dL_dscales, dL_drot,
-                dL_dcov3D if has_cov else None, None, None, None, dL_ddc) + cam_grads
+                dL_dcov3D if has_cov else None, None, None, None, dL_ddc) + cam_grads + (dL_dbg, None)
 
 
 def _cpu_copy(args):
@@ -540,23 +593,30 @@ def _cpu_copy(args):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, tile_rows: Optional[Tuple[int, int]] = None, grad_sync=None, dc=None):
+                        raster_settings, tile_rows: Optional[Tuple[int, int]] = None, grad_sync=None, dc=None, return_alpha: bool = False):
     """Functional form.  `grad_sync(records[P,12])`, if given, is called between the blend backward and the
     per-Gaussian backward (multi-GPU: all-reduce of the 48-byte gradient records, parallel.py).
     `tile_rows=(y0, y1)` (extension) restricts binning + blending to that
     band of 16-pixel tile rows; pixels outside the band come back as zeros.  `dc` (the reference's separate_sh
     form): SH coefficient 0 as [P,1,3]; `sh` then holds coefficients 1.. as [P,M-1,3].
     Camera gradients (no reference counterpart): when raster_settings.viewmatrix / projmatrix / campos require grad, backward
-    returns their gradients too (include/gsr.h gsr_backward_preprocess_camera; with `tile_rows`, the band's contribution)."""
+    returns their gradients too (include/gsr.h gsr_backward_preprocess_camera; with `tile_rows`, the band's contribution).
+    Alpha image and background (no reference counterpart, include/gsr.h gsr_rasterize_forward_composite): `return_alpha=True` returns
+    `(color, radii, invdepth, alpha)` with the differentiable accumulated opacity alpha[1,H,W] = 1 - T_final.  raster_settings.bg may be
+    [3] or a per-pixel image [3,H,W]; when it requires grad, backward returns its gradient (with `tile_rows`, the band's contribution).
+    Not available with `grad_sync` (GsrError)."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, tile_rows, grad_sync, dc, raster_settings.viewmatrix,
-                                     raster_settings.projmatrix, raster_settings.campos)
+                                     raster_settings.projmatrix, raster_settings.campos, raster_settings.bg, bool(return_alpha))
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False):
+        """`return_alpha=True` (opt-in, no reference counterpart): the call returns `(color, radii, invdepth, alpha)`, alpha[1,H,W] being the
+        differentiable accumulated opacity 1 - T_final (rasterize_gaussians)."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.return_alpha = bool(return_alpha)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """bool[P]: in front of the near plane (the reference's mark_visible / checkFrustum)."""
@@ -572,7 +632,7 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, getattr(self, "tile_rows", None), None, dc)
+                                   self.raster_settings, getattr(self, "tile_rows", None), None, dc, self.return_alpha)
 
 
 class SparseGaussianAdam(torch.optim.Adam):

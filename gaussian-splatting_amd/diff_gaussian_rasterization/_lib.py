@@ -65,6 +65,17 @@ class CameraGrads(C.Structure):
     _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class CompositeOut(C.Structure):
+    """GsrCompositeOut of include/gsr.h (gsr_rasterize_forward_composite)."""
+    _fields_ = [("out_alpha", C.c_void_p), ("bg_image", C.c_void_p)]
+
+
+class CompositeGrads(C.Structure):
+    """GsrCompositeGrads of include/gsr.h (gsr_backward_blend_composite)."""
+    _fields_ = [("dL_dout_alpha", C.c_void_p), ("bg_image", C.c_void_p), ("dL_dbg_image", C.c_void_p), ("dL_dbg", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 class AdamTensor(C.Structure):
     """GsrAdamTensor of include/gsr.h (gsr_adam_step_multi)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
@@ -97,6 +108,9 @@ SIGNATURES = {
     "gsr_backward_preprocess": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 10 + [_vp] * 9),
     "gsr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_backward_preprocess_camera": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 10 + [_vp] * 8 + [C.POINTER(CameraGrads), _vp]),
+    "gsr_rasterize_forward_composite": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 7 + _BUFFERS + [_vp, _vp, _vp, _i32p, C.POINTER(CompositeOut), _vp]),
+    "gsr_composite_grad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gsr_backward_blend_composite": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), C.POINTER(CompositeGrads), _vp]),
     "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
     "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
     "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -226,9 +226,10 @@ def render_sharded(render_band: Callable, inputs: Sequence, plan: BandPlan, grou
 
 
 def _camera_detached(raster_settings):
-    """The multi-GPU forms return no camera gradient: viewmatrix / projmatrix / campos enter them detached (a per-band partial camera
-    gradient without an all-reduce would be wrong, and summing it is out of scope)."""
-    t = {k: getattr(raster_settings, k) for k in ("viewmatrix", "projmatrix", "campos")}
+    """The multi-GPU forms return no camera and no background gradient: viewmatrix / projmatrix / campos / bg enter them detached (a
+    per-band partial gradient without an all-reduce would be wrong, and summing it is out of scope).  They take the constant
+    background [3] only: a per-pixel image [3,H,W] is refused (GsrError, _make_settings), and there is no alpha output."""
+    t = {k: getattr(raster_settings, k) for k in ("viewmatrix", "projmatrix", "campos", "bg")}
     if not any(isinstance(v, torch.Tensor) and v.requires_grad for v in t.values()):
         return raster_settings
     return raster_settings._replace(**{k: v.detach() for k, v in t.items()})

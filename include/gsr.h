@@ -205,6 +205,56 @@ int gsr_backward_preprocess_camera(const GsrRasterSettings* settings, int P, int
                                    float* dL_dscales, float* dL_drotations, const GsrCameraGrads* camera, void* stream);
 
 /*
+ * Differentiable alpha image and per-pixel / learnable background (no reference counterpart): gsr_rasterize_forward and
+ * gsr_backward_blend with one extra struct.  Per pixel, over the contributors i the forward blends (the same skip, 0.99 cap and
+ * termination rules, nothing new):
+ *   T_final = prod_i (1 - alpha_i)                          the transmittance the forward freezes at termination
+ *   alpha   = 1 - T_final                                   out_alpha[1,H,W]
+ *   color   = sum_i c_i alpha_i T_i + T_final * B(pixel)    B = settings->bg[3] broadcast, or bg_image[3,H,W] when given
+ * Backward, in addition to what gsr_backward_blend computes:
+ *   dL/dalpha_i            += (-T_final / (1 - alpha_i)) * (<B(pixel), dL/dC(pixel)> - dL/dalpha_image(pixel))
+ *   dL_dbg_image[c][pixel]  = T_final(pixel) * dL/dC[c][pixel]     every pixel, also where no Gaussian contributes (T_final = 1)
+ *   dL_dbg[c]               = sum over the pixels of the line above (fp64 products and sums in a fixed order, one rounding to fp32)
+ * Conventions: those of the other gradients -- no gradient through culling, radii, tile assignment, depth order or the
+ * alpha >= 1/255 and T < 1e-4 cut-offs; the 0.99 cap is passed straight through as for colour.  With a band of tile rows
+ * (tile_y0 / tile_y1) out_alpha is written inside the band only (like out_color), and dL_dbg_image / dL_dbg are the band's
+ * contribution: zero outside it.  P == 0: the composite forward writes alpha = 0 and color = B (gsr_rasterize_forward keeps the
+ * reference's zero image), and the backward writes dL_dbg_image = dL/dC and its sum; it needs no state buffer then.
+ * Every optional pointer may be NULL; with all of them NULL the two calls write the same bits as gsr_rasterize_forward /
+ * gsr_backward_blend for P > 0, and a NULL `extra` itself is GSR_ERR_INVALID_ARG.  settings->bg must stay a valid pointer; it is not read
+ * when bg_image is given.  The backward's bg_image must be the forward's.  dL_dbg_image and dL_dbg are OVERWRITTEN, bit-reproducible
+ * (no atomics); dL_dbg needs `scratch`: device memory of gsr_composite_grad_scratch_bytes(width, height) bytes, 8-byte aligned.
+ * The [P,12] records keep their layout, so gsr_backward_preprocess, gsr_backward_preprocess_camera and
+ * gsr_backward_preprocess_sh_adam all follow gsr_backward_blend_composite unchanged.
+ */
+typedef struct GsrCompositeOut {
+    float* out_alpha;             /* [1,H,W] or NULL */
+    const float* bg_image;        /* [3,H,W] or NULL (then settings->bg) */
+} GsrCompositeOut;
+int gsr_rasterize_forward_composite(const GsrRasterSettings* settings, int P, int M,
+                                    const float* means3D, const float* shs, const float* colors_precomp,
+                                    const float* opacities, const float* scales, const float* rotations,
+                                    const float* cov3D_precomp,
+                                    GsrResizeFn geom_resize, void* geom_user,
+                                    GsrResizeFn binning_resize, void* binning_user,
+                                    GsrResizeFn image_resize, void* image_user,
+                                    float* out_color, float* out_invdepth, int32_t* radii,
+                                    int32_t* num_rendered, const GsrCompositeOut* extra, void* stream);
+typedef struct GsrCompositeGrads {
+    const float* dL_dout_alpha;   /* [1,H,W] or NULL (treated as zero) */
+    const float* bg_image;        /* as in the forward */
+    float* dL_dbg_image;          /* [3,H,W] or NULL */
+    float* dL_dbg;                /* [3] or NULL */
+    void* scratch;                /* gsr_composite_grad_scratch_bytes(width, height); needed for dL_dbg only */
+} GsrCompositeGrads;
+size_t gsr_composite_grad_scratch_bytes(int width, int height);
+int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                                 const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                 const float* dL_dout_color, const float* dL_dout_invdepth,
+                                 void* bwd_scratch, float** splat_grads_out,
+                                 const GsrCompositeGrads* extra, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
