@@ -417,7 +417,7 @@ int gsr_set_option(const char* name, int value) {
         gsr_set_ssim_variant(value);
         return GSR_OK;
     }
-    if (!strcmp(name, "ssim_target_waves")) { gsr_set_ssim_target_waves(value); return GSR_OK; }
+    if (!strcmp(name, "ssim_target_waves")) { gsr_set_ssim_target_waves(value); return GSR_OK; }      // (0 = the defaults, forward 4096 / backward 2048)
     if (!strcmp(name, "snug_tiles")) {
         if (value != 0 && value != 1) return fail(GSR_ERR_INVALID_ARG, "snug_tiles must be 1 (snug tile rectangles) or 0 (the reference's tile square)");
         g_snug_tiles = value;

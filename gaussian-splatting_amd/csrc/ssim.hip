@@ -45,11 +45,14 @@ constexpr int STAGE_PAD = (NSTAGE * 256 + HX - 1) / HX - HY;        // 2 spare r
 constexpr float C1 = 0.01f * 0.01f;
 constexpr float C2 = 0.03f * 0.03f;
 
-// normalised 11-tap Gaussian, sigma = 1.5 (utils/loss_utils.py:43-46), rounded from fp64
+// normalised 11-tap Gaussian, sigma = 1.5 (utils/loss_utils.py:43-46), each tap the fp32 nearest to its fp64 value: the eleven sum to
+// 1 - 1.4e-9.  (Until the loss tests on smooth content, taps 4 / 6 were one ulp low -- 2.1300552785e-01 -- and the window summed to 1 - 3.1e-8:
+// sigma^2 = E[x^2] - mu^2 of a flat patch of level c came out as +6.2e-8 c^2 instead of 0, which next to C2 = 9e-4 biased the mean SSIM of
+// smooth images by 3e-6 .. 6e-6, ten times the fp32 formula's own error.)
 #define GSR_WIN(k)                                                                                                        \
     ((k) == 0 || (k) == 10 ? 1.0283801239e-03f : (k) == 1 || (k) == 9 ? 7.5987582095e-03f                                \
      : (k) == 2 || (k) == 8 ? 3.6000773311e-02f : (k) == 3 || (k) == 7 ? 1.0936068743e-01f                                \
-     : (k) == 4 || (k) == 6 ? 2.1300552785e-01f : 2.6601171494e-01f)
+     : (k) == 4 || (k) == 6 ? 2.1300554276e-01f : 2.6601171494e-01f)
 
 // MEAN: instead of the SSIM map the workgroup writes the SUM of its tile's SSIM values (partials[plane][tile]); a second
 // one-workgroup kernel adds the partials in fixed order -> mean (deterministic, no 25 MB map round trip, no torch reduce)
@@ -170,7 +173,7 @@ ssim_fwd_kernel(int H, int W, int planes, const float* __restrict__ img1, const 
             if (MODE == 2) l1_own += fabsf(s_x[4 * rg + o + HALO][cx + HALO] - s_y[4 * rg + o + HALO][cx + HALO]);
             const float mu1 = acc[o][0], mu2 = acc[o][1], ex2 = acc[o][2], ey2 = acc[o][3], exy = acc[o][4];
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float sigma1_sq = ex2 - mu1_sq, sigma2_sq = ey2 - mu2_sq, sigma12 = exy - mu12;
+            const float sigma1_sq = fmaf(-mu1, mu1, ex2), sigma2_sq = fmaf(-mu2, mu2, ey2), sigma12 = fmaf(-mu2, mu1, exy);
             const float A = mu1_sq + mu2_sq + C1, B = sigma1_sq + sigma2_sq + C2;
             const float Cc = 2.f * mu12 + C1, D = 2.f * sigma12 + C2;
             const float inv_AB = 1.f / (A * B);
@@ -481,7 +484,9 @@ ssim_fwd_march(int H, int W, int planes, int nsx, int nsy, int seg, const float*
             const uint32_t off = valid ? (uint32_t)o * row4 + col4 : OOB;
             const float mu1 = A[0][0], mu2 = A[1][0], ex2 = A[2][0], ey2 = A[3][0], exy = A[4][0];
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float sigma1_sq = ex2 - mu1_sq, sigma2_sq = ey2 - mu2_sq, sigma12 = exy - mu12;
+            const float sigma1_sq = fmaf(-mu1, mu1, ex2), sigma2_sq = fmaf(-mu2, mu2, ey2), sigma12 = fmaf(-mu2, mu1, exy);
+            // (the three fmaf: the cancellation with ONE rounding.  hipcc contracts `ex2 - mu1 * mu1` to this v_fma_f32 anyway -- the gfx950 code is
+            //  unchanged -- but a build without contraction, as the host build of the tests, rounded mu^2 first: 1.6x the error of the mean SSIM on edges)
             const float Aa = mu1_sq + mu2_sq + C1, B = sigma1_sq + sigma2_sq + C2;
             const float Cc = 2.f * mu12 + C1, D = 2.f * sigma12 + C2;
             const float inv_A = __builtin_amdgcn_rcpf(Aa), inv_B = __builtin_amdgcn_rcpf(B);
@@ -623,7 +628,8 @@ ssim_bwd_march(int H, int W, int planes, int nsx, int nsy, int seg, const float*
 
 int g_ssim_variant = 0;           // 0 = marching waves, 1 = LDS tiles (A/B)
 // waves a launch of the marching form aims for (1024 SIMDs x waves per SIMD): [0] forward kernels, [1] backward kernels
-int g_ssim_target_waves[2] = {4096, 2048};
+constexpr int SSIM_TARGET_WAVES_FWD = 4096, SSIM_TARGET_WAVES_BWD = 2048;
+int g_ssim_target_waves[2] = {SSIM_TARGET_WAVES_FWD, SSIM_TARGET_WAVES_BWD};
 
 struct MarchPlan { int nsx, nsy, seg; unsigned lds; };
 // Launch shape.  A launch has FEWER waves than the chip has slots for, and the dispatcher fills a CU to its limit before it
@@ -671,7 +677,11 @@ static bool ssim_use_tiles(int H, int W, bool mean_without_maps) {
 }
 
 void gsr_set_ssim_variant(int v) { g_ssim_variant = v; }
-void gsr_set_ssim_target_waves(int v) { g_ssim_target_waves[0] = g_ssim_target_waves[1] = std::max(v, 256); }
+// 0 restores the defaults (forward and backward differ, so no single value can); any other value goes into both slots
+void gsr_set_ssim_target_waves(int v) {
+    if (v == 0) { g_ssim_target_waves[0] = SSIM_TARGET_WAVES_FWD; g_ssim_target_waves[1] = SSIM_TARGET_WAVES_BWD; return; }
+    g_ssim_target_waves[0] = g_ssim_target_waves[1] = std::max(v, 256);
+}
 
 /* the tiled form also serves the mean forms WITHOUT derivative maps (no-grad evaluation): with nothing to store per row the  \
    marching loop compiles to 170+ registers */                                                                                    \

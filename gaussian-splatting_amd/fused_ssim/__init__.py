@@ -21,12 +21,19 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _check_pair(what, img1, img2):
+    """The kernels index both images with img1's shape: a smaller img2 would be read out of bounds."""
+    if not img1.is_cuda or not img2.is_cuda:
+        raise _lib.GsrError(f"{what} needs HIP tensors ('cuda'); there is no CPU path")
+    if img1.shape != img2.shape:
+        raise _lib.GsrError(f"{what}: the two images differ in shape: {tuple(img1.shape)} and {tuple(img2.shape)}")
+
+
 class FusedSSIMMap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, train=True):
         lib = _lib.load()
-        if not img1.is_cuda or not img2.is_cuda:
-            raise _lib.GsrError("fused_ssim needs HIP tensors ('cuda'); there is no CPU path")
+        _check_pair("fused_ssim", img1, img2)
         a = img1.contiguous().float()
         b = img2.contiguous().float()
         Bn, Cn, H, W = a.shape
@@ -68,8 +75,7 @@ class FusedSSIMMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, train=True):
         lib = _lib.load()
-        if not img1.is_cuda or not img2.is_cuda:
-            raise _lib.GsrError("fused_ssim needs HIP tensors ('cuda'); there is no CPU path")
+        _check_pair("fused_ssim", img1, img2)
         a = img1.contiguous().float()
         b = img2.contiguous().float()
         Bn, Cn, H, W = a.shape
@@ -114,8 +120,7 @@ class FusedTrainLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, lambda_dssim):
         lib = _lib.load()
-        if not img1.is_cuda or not img2.is_cuda:
-            raise _lib.GsrError("fused_train_loss needs HIP tensors ('cuda'); there is no CPU path")
+        _check_pair("fused_train_loss", img1, img2)
         a = img1.contiguous().float()
         b = img2.contiguous().float()
         Bn, Cn, H, W = a.shape
