@@ -5,7 +5,8 @@
 Translation units and their flags:
   preprocess.hip   -ffp-contract=off   (bit-exact radii / tile counts, see csrc/gsr_math.h)
   sort.hip, depthsort.hip, binning.hip (integer)
-  render_fwd.hip, render_bwd.hip       (FMA contraction allowed; image tolerance 1e-5)
+  render_fwd.hip, render_bwd.hip,
+  contrib.hip                          (FMA contraction allowed; image tolerance 1e-5)
   gsr_api.cpp                          (host glue, C ABI)
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
 """
@@ -41,6 +42,7 @@ UNITS = [
     # -fno-slp-vectorize: automatic v_pk_*_f32 packing costs more issue slots than it saves on gfx950 (forward blend -3 %)
     ("render_fwd.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("render_bwd.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
+    ("contrib.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("adam.hip", ["-ffp-contract=off"]),
     # no SLP vectorisation: the auto-packed v_pk_fma_f32 and the v_mov shuffles that assemble their operand pairs cost more
     # issue slots than the scalar FMAs they replace (forward 60.2 -> 55.3 us on one box); the per-Gaussian kernels were

@@ -1130,6 +1130,41 @@ int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32
                           splat_grads_out, extra, stream);
 }
 
+size_t gsr_contribution_scratch_bytes(int P, int64_t R) { (void)P; return gsr_carve_contrib(nullptr, R).bytes; }
+
+int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                           const void* binning_buffer, const void* image_buffer, const float* pixel_weight, void* scratch,
+                           const GsrContribOut* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GsrCamDev cam;
+    int rc = make_cam(settings, 0, cam);
+    if (rc != GSR_OK) return rc;
+    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
+    if (!out) return fail(GSR_ERR_INVALID_ARG, "out (GsrContribOut) is NULL");
+    if (out->accumulate != 0 && out->accumulate != 1) return fail(GSR_ERR_INVALID_ARG, "GsrContribOut.accumulate must be 0 or 1");
+    const int64_t R = num_rendered;
+    if (R > 0 && !scratch) return fail(GSR_ERR_INVALID_ARG, "scratch is NULL (gsr_contribution_scratch_bytes)");
+    if (((uintptr_t)scratch) & 15) return fail(GSR_ERR_INVALID_ARG, "contribution scratch must be 16-byte aligned");
+    if (P > 0 && R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
+    if (!out->accumulate && P > 0) {      // every row is written: Gaussians without instances keep these zeros
+        if (out->weight_sum) HIP_OK(hipMemsetAsync(out->weight_sum, 0, (size_t)P * sizeof(float), st));
+        if (out->weight_max) HIP_OK(hipMemsetAsync(out->weight_max, 0, (size_t)P * sizeof(float), st));
+        if (out->pixel_count) HIP_OK(hipMemsetAsync(out->pixel_count, 0, (size_t)P * sizeof(int32_t), st));
+    }
+    if (P == 0 || R == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
+    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
+    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
+    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
+    const int list_buf = list_buffer_index(cam.gx * cam.gy);
+    gsr_launch_contribution_stats(cam, P, R, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, g.vals[depth_order_buffer_index()], g.offsets,
+                                  pixel_weight, gsr_carve_contrib((char*)scratch, R), out->weight_sum, out->weight_max, out->pixel_count,
+                                  out->accumulate, st);
+    STAGE_CHECK("contribution statistics");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 // gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera
 static int backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
                                const float* colors_precomp, const float* opacities, const float* scales,

@@ -324,6 +324,19 @@ struct GsrBwdScratch {
 };
 GsrBwdScratch gsr_carve_bwd(char* base, int P, int64_t R);
 
+// contrib.hip: per-Gaussian blend-weight statistics (gsr_contribution_stats).  Scratch (caller-owned, gsr_contribution_scratch_bytes): one
+// 16-byte record slot per (8x8 block of the tile, instance), slot-major, and a flag word per instance -- 68 R bytes, so every offset is 64-bit
+struct GsrContribScratch {
+    float4* slots;          // [4][R]  (sum, max, count bits, -) of the block's pixels
+    uint32_t* flags;        // [R]     byte q != 0: slot q of the instance has a record
+    size_t bytes;
+};
+GsrContribScratch gsr_carve_contrib(char* base, int64_t R);
+void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list, const float4* splats,
+                                   const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets, const float* pixel_weight /*[H*W] or NULL*/,
+                                   const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count /*each [P] or NULL*/,
+                                   int accumulate, hipStream_t st);
+
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                      int step, hipStream_t st);

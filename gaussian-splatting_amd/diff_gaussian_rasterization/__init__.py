@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import GsrError, GsrRasterSettings, RESIZE_FN  # noqa: F401
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam", "rasterize_gaussians", "GsrError"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam", "rasterize_gaussians", "GsrError",
+           "ContributionStats", "contribution_stats"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -306,6 +307,89 @@ def _rasterize_backward(s, P, M, inputs, radii, fwd: _Forward, g_color, g_depth,
     _lib.check(lib.gsr_rasterize_backward(C.byref(s), P, M, fwd.num_rendered, *[_ptr(t) for t in inputs], _ptr(radii), _ptr(fwd.geom),
                                           _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color), _ptr(g_depth), *[_ptr(g) for g in grads],
                                           _ptr(scratch), None, _stream_ptr(device)), "gsr_rasterize_backward")
+
+
+class ContributionStats(NamedTuple):
+    """Per-Gaussian blend-weight statistics of one or more forwards (include/gsr.h gsr_contribution_stats): with w = alpha * T, the
+    forward's blend weight, and a per-pixel weight E: weight_sum[P] = sum_p E w, weight_max[P] = max(0, max_p E w) (float32) and
+    pixel_count[P] = pixels with E != 0 the Gaussian was blended into (int32)."""
+    weight_sum: torch.Tensor
+    weight_max: torch.Tensor
+    pixel_count: torch.Tensor
+
+
+def _pixel_weight(pixel_weight, H: int, W: int, device) -> Optional[torch.Tensor]:
+    if pixel_weight is None:
+        return None
+    if tuple(pixel_weight.shape) not in ((H, W), (1, H, W)):
+        raise GsrError(f"pixel_weight must have shape [{H}, {W}] or [1, {H}, {W}] (image_height, image_width), got {list(pixel_weight.shape)}")
+    if pixel_weight.device != device:
+        raise GsrError(f"pixel_weight lives on {pixel_weight.device}, the rendered state on {device}")
+    return _f32c(pixel_weight.detach())
+
+
+def _contribution_stats(s, P, fwd: _Forward, pixel_weight, into: Optional[ContributionStats], device) -> ContributionStats:
+    """gsr_contribution_stats on the state a tracking forward left: fresh arrays, or `into` combined in place."""
+    lib = _lib.load()
+    if into is None:
+        out = ContributionStats(torch.empty(P, dtype=torch.float32, device=device), torch.empty(P, dtype=torch.float32, device=device),
+                                torch.empty(P, dtype=torch.int32, device=device))
+    else:
+        out = into
+        for t, dt, name in zip(out, (torch.float32, torch.float32, torch.int32), ContributionStats._fields):
+            if tuple(t.shape) != (P,) or t.dtype != dt or t.device != device or not t.is_contiguous():
+                raise GsrError(f"into.{name} must be a contiguous {dt} tensor of shape [{P}] on {device}")
+    scratch = torch.empty(_sized("contrib", device, lib.gsr_contribution_scratch_bytes(P, fwd.num_rendered)), dtype=torch.uint8, device=device)
+    rec = _lib.ContribOut(out.weight_sum.data_ptr(), out.weight_max.data_ptr(), out.pixel_count.data_ptr(), 0 if into is None else 1, 0)
+    _lib.check(lib.gsr_contribution_stats(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(pixel_weight),
+                                          _ptr(scratch), C.byref(rec), _stream_ptr(device)), "gsr_contribution_stats")
+    return out
+
+
+def _rasterizer_nodes(t: torch.Tensor) -> list:
+    """The _RasterizeGaussians nodes of the autograd graph behind `t` (the node of an autograd.Function is its ctx)."""
+    found, seen, stack = [], set(), [t.grad_fn]
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        if isinstance(fn, _RasterizeGaussians._backward_cls):
+            found.append(fn)
+            continue      # (what fed the rasterizer is not a render of it)
+        stack.extend(f for f, _ in fn.next_functions)
+    return found
+
+
+def contribution_stats(rendered: torch.Tensor, pixel_weight: Optional[torch.Tensor] = None,
+                       into: Optional[ContributionStats] = None) -> ContributionStats:
+    """What every Gaussian gave to a frame that has ALREADY been rendered (no reference counterpart): `rendered` is any tensor computed
+    from one rasterizer call's outputs with gradients enabled -- the reference's `render(...)["render"]`, after exposure and clamp --
+    and the statistics are read from the state that call keeps for its backward: no second forward, no backward.  Call it BEFORE
+    `backward()` frees that state (or use `retain_graph=True`).  `pixel_weight` [H,W] or [1,H,W] weights the pixels (a per-pixel error,
+    a mask: pixels with weight 0 are excluded); None is 1 everywhere.  `into` (a ContributionStats of an earlier call) is combined in
+    place -- sum + frame, max(max, frame), count + frame -- and returned, so scores over many views build up without torch ops.
+    With `tile_rows` the statistics are the band's.  Nothing here is differentiable; two calls give the same bits."""
+    nodes = _rasterizer_nodes(rendered) if isinstance(rendered, torch.Tensor) else []
+    if len(nodes) != 1:
+        raise GsrError(("no rasterizer call found behind `rendered`: it must be computed from a GaussianRasterizer output with gradients enabled "
+                        "(under torch.no_grad() use GaussianRasterizer.contributions)") if not nodes else
+                       f"`rendered` depends on {len(nodes)} rasterizer calls: pass a tensor computed from exactly one")
+    ctx = nodes[0]
+    if ctx.grad_sync is not None:
+        raise GsrError("contribution_stats does not support the multi-GPU renderers (a rasterizer call with grad_sync)")
+    try:
+        saved = ctx.saved_tensors
+    except RuntimeError as e:
+        raise GsrError("the rasterizer call's state has been freed: call contribution_stats before backward(), or use retain_graph=True") from e
+    means3D, geom, binning, img = saved[0], saved[8], saved[9], saved[10]
+    device, P = means3D.device, int(means3D.shape[0])
+    rs = ctx.raster_settings
+    pw = _pixel_weight(pixel_weight, int(rs.image_height), int(rs.image_width), device)
+    keep: list = []
+    with torch.no_grad(), torch.cuda.device(device):
+        s = _make_settings(rs, keep, ctx.tile_rows, bg_image=True)
+        return _contribution_stats(s, P, _Forward(geom, binning, img, ctx.num_rendered), pw, into, device)
 
 
 def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
@@ -633,6 +717,33 @@ class GaussianRasterizer(nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, getattr(self, "tile_rows", None), None, dc, self.return_alpha)
+
+
+    def contributions(self, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, pixel_weight=None,
+                      into: Optional[ContributionStats] = None):
+        """-> (ContributionStats, radii[P]): the statistics of `contribution_stats` for this camera without a render of one's own to hand
+        (no reference counterpart): runs a tracking forward with zero colours under no_grad, honours `tile_rows`, keeps nothing."""
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _lib.load()
+        _require_cuda(means3D, "means3D")
+        rs = self.raster_settings
+        device, P = means3D.device, int(means3D.shape[0])
+        H, W = int(rs.image_height), int(rs.image_width)
+        pw = _pixel_weight(pixel_weight, H, W, device)
+        keep: list = []
+        with torch.no_grad(), torch.cuda.device(device):
+            tile_rows = getattr(self, "tile_rows", None)
+            s = _make_settings(rs, keep, tile_rows, no_backward=False, bg_image=True)
+            inputs = (_f32c(means3D.detach()), None, torch.zeros(P, 3, dtype=torch.float32, device=device), _f32c(opacities.detach()),
+                      _f32c(scales.detach()) if scales is not None else None, _f32c(rotations.detach()) if rotations is not None else None,
+                      _f32c(cov3D_precomp.detach()) if cov3D_precomp is not None else None)
+            color = torch.empty(3, H, W, dtype=torch.float32, device=device)
+            invdepth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+            radii = torch.empty(P, dtype=torch.int32, device=device)
+            fwd = _rasterize_forward(s, P, 0, inputs, color, invdepth, radii, device)
+            return _contribution_stats(s, P, fwd, pw, into, device), radii
 
 
 class SparseGaussianAdam(torch.optim.Adam):

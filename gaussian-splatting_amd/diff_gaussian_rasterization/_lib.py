@@ -76,6 +76,12 @@ class CompositeGrads(C.Structure):
                 ("scratch", C.c_void_p)]
 
 
+class ContribOut(C.Structure):
+    """GsrContribOut of include/gsr.h (gsr_contribution_stats)."""
+    _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("pixel_count", C.c_void_p), ("accumulate", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class AdamTensor(C.Structure):
     """GsrAdamTensor of include/gsr.h (gsr_adam_step_multi)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
@@ -111,6 +117,8 @@ SIGNATURES = {
     "gsr_rasterize_forward_composite": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 7 + _BUFFERS + [_vp, _vp, _vp, _i32p, C.POINTER(CompositeOut), _vp]),
     "gsr_composite_grad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "gsr_backward_blend_composite": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), C.POINTER(CompositeGrads), _vp]),
+    "gsr_contribution_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "gsr_contribution_stats": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.POINTER(ContribOut), _vp]),
     "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
     "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
     "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -255,6 +255,41 @@ int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32
                                  const GsrCompositeGrads* extra, void* stream);
 
 /*
+ * Per-Gaussian blend-weight statistics (no reference counterpart): what each Gaussian GAVE to the image of one forward -- the
+ * importance scores of pruning (sum or max of alpha T), error-weighted densification scores and hit counts -- read from the state
+ * that gsr_rasterize_forward / gsr_rasterize_forward_composite leave when run with no_backward == 0 (the same settings, the same
+ * buffers, num_rendered as returned).  The states of the record entry points (from_splats / from_packed / from_segments) are not
+ * supported.  Nothing is differentiable.
+ * Gaussian i contributes to pixel p of the rendered band exactly when the forward blended it there: its entry is valid
+ * (power <= 0 and alpha >= 1/255, alpha capped at 0.99) and its list position is <= n_contrib[p]; n_contrib is the authority on
+ * termination (T < 1e-4 is not re-tested).  w_ip = alpha_ip * T_ip, T_ip the product of (1 - alpha) over the valid entries in
+ * front of it: the forward's blend weight.  E = pixel_weight[H,W], NULL meaning 1 everywhere; a pixel with E(p) == 0 is excluded
+ * from all three statistics, so E also serves as a mask.
+ *   weight_sum[i]  = sum_p E(p) w_ip
+ *   weight_max[i]  = max(0, max_p E(p) w_ip)
+ *   pixel_count[i] = number of pixels p with E(p) != 0 that i contributes to
+ * Every one of the P rows is written (zeros for culled and non-contributing Gaussians).  accumulate == 1 combines the frame's
+ * finished per-Gaussian value with the stored one instead: sum <- sum + frame (one fp32 add), max <- max(max, frame),
+ * count <- count + frame -- scores over many views build up in place.  P == 0 or num_rendered == 0: zeros with accumulate == 0,
+ * the arrays left as they are with accumulate == 1.  With a band of tile rows (tile_y0 / tile_y1) the statistics are the band's
+ * contribution.  Bit-reproducible: no atomics, every sum in a fixed order.  Each output pointer may be NULL.
+ * `scratch`: device memory of gsr_contribution_scratch_bytes(P, num_rendered) bytes, 16-byte aligned, contents undefined before and
+ * after.  A NULL `out`, or a NULL scratch with num_rendered > 0, is GSR_ERR_INVALID_ARG.
+ */
+typedef struct GsrContribOut {
+    float*   weight_sum;    /* [P] or NULL */
+    float*   weight_max;    /* [P] or NULL */
+    int32_t* pixel_count;   /* [P] or NULL */
+    int32_t  accumulate;    /* 0 overwrite, 1 combine as defined above */
+    int32_t  reserved;
+} GsrContribOut;
+size_t gsr_contribution_scratch_bytes(int P, int64_t R);
+int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                           const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                           const float* pixel_weight /* [H,W] or NULL */, void* scratch,
+                           const GsrContribOut* out, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
