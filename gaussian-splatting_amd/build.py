@@ -6,8 +6,10 @@ Translation units and their flags:
   preprocess.hip   -ffp-contract=off   (bit-exact radii / tile counts, see csrc/gsr_math.h)
   sort.hip, depthsort.hip, binning.hip (integer)
   render_fwd.hip, render_bwd.hip,
-  contrib.hip                          (FMA contraction allowed; image tolerance 1e-5)
+  contrib.hip                          (FMA contraction allowed; image tolerance 1e-5; what the three must compute identically -- box
+                                        test, exponent / alpha -- is csrc/gsr_blend.h, their wave reductions csrc/gsr_wave.h)
   gsr_api.cpp                          (host glue, C ABI)
+UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
 """
 from __future__ import annotations

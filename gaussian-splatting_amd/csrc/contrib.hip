@@ -8,7 +8,7 @@
 //
 //  contrib_walk     one wave64 per 8x8 pixel block, front to back, the forward's structure (render_fwd_wave_bf): ids two batches ahead, the
 //                   64-byte record gather one batch ahead, the forward's exact box test, the survivors parked compacted in the wave's LDS, then the
-//                   lanes act as pixel lanes with blend_step_bf's expressions for p2, alpha and testT.  n_contrib is the authority on who
+//                   lanes act as pixel lanes with the forward's p2 and alpha (gsr_blend.h) and its testT.  n_contrib is the authority on who
 //                   contributed: a pixel takes a valid entry (power <= 0, alpha >= 1/255) exactly when its list position is <= n_contrib[p],
 //                   T < 1e-4 is not re-tested, and the wave walks no further than the largest n_contrib of its pixels.  A pixel with
 //                   E(p) == 0 -- or outside the image -- takes part with n_contrib = 0.  Per survivor the 64 values E w are summed and
@@ -28,52 +28,10 @@
 // Known cost: a wave of the reduce whose 64 Gaussians hold one very large splat streams all its chunks alone (the tail the blend
 // backward's unit-based reduce was built to avoid); chunks without flags -- most of such a splat -- cost one coalesced flag read each.
 #include "gsr_internal.h"
+#include "gsr_blend.h"
+#include "gsr_wave.h"
 
 namespace {
-
-// (render_fwd.hip's helper, verbatim: the walk must drop exactly the entries the forward dropped)
-__device__ __forceinline__ float min_q_over_box(float mx, float my, float A, float B, float C, float x0, float x1,
-                                                float y0, float y1) {
-    const float lx = x0 - mx, hx = x1 - mx, ly = y0 - my, hy = y1 - my;   // box in centre-relative coords
-    const bool in_x = (lx <= 0.0f) && (hx >= 0.0f);
-    const bool in_y = (ly <= 0.0f) && (hy >= 0.0f);
-    float q = 3.0e38f;
-    if (in_x && in_y) return 0.0f;
-    if (!in_x) {
-        const float dx = lx > 0.0f ? lx : hx;                 // facing vertical edge
-        const float dy = fminf(hy, fmaxf(ly, -B * dx * __builtin_amdgcn_rcpf(C)));   // clamped optimum along it (tau carries a 0.01 margin: v_rcp_f32's ulp is harmless)
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    if (!in_y) {
-        const float dy = ly > 0.0f ? ly : hy;
-        const float dx = fminf(hx, fmaxf(lx, -B * dy * __builtin_amdgcn_rcpf(A)));
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    return q;
-}
-
-// q3 of the splat record = (rect.x bits, rect.y bits, first emission index bits, tiles bits), see preprocess.hip / binning.hip
-__device__ __forceinline__ uint32_t emission_index(const float4 q3, uint32_t tx, uint32_t ty) {
-    const uint32_t rx = __float_as_uint(q3.x), ry = __float_as_uint(q3.y), goff = __float_as_uint(q3.z);
-    const uint32_t minx = rx & 0xFFFFu, w = (rx >> 16) - minx, miny = ry & 0xFFFFu;
-    return goff + (ty - miny) * w + (tx - minx);
-}
-
-// the six DPP stages of a wave reduction to lane 63 (render_bwd.hip wave_sum_to_lane63): full row mask and bound_ctrl, a lane without a
-// source reads 0
-template <int CTRL>
-__device__ __forceinline__ float dpp_moved(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-// The maximum runs on the BIT PATTERNS of values clamped at 0 first: non-negative floats order like their bits, +0 (what a lane without a source reads) is
-// the smallest of them, and an integer maximum needs no NaN canonicalisation of its operands -- one v_max_u32_dpp per stage.
-template <int CTRL>
-__device__ __forceinline__ void sum_max_stage(float& s, uint32_t& m) {
-    s = s + dpp_moved<CTRL>(s);
-    m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, CTRL, 0xf, 0xf, true));
-}
-
-constexpr float LOG2E = 1.4426950408889634f;
 
 __global__ void __launch_bounds__(64)
 contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
@@ -81,16 +39,13 @@ contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, 
              float4* __restrict__ slots /*[4][R] (sum, max, count bits, -)*/, uint8_t* __restrict__ slot_flags /*[R][4]*/, int64_t R) {
     __shared__ float4 s_rec[64 * 2];      // the batch's survivors, compacted: (x, y, a2, b2) (c2, opacity, lane bits, -)
     __shared__ float4 s_out[64];          // per entry of the batch (by lane): (sum, max, count bits, -)
-    // the forward's mapping: the four 8x8 blocks of a tile get ids b, b+8, b+16, b+24 -> same XCD -> they share the gathered records in L2
-    const int b = blockIdx.x;
-    const int grp = b >> 5, r32 = b & 31;
-    const int tile_local = grp * 8 + (r32 & 7);
-    const int quad = r32 >> 3;
+    const gsrb::TileQuad tq = gsrb::block8_of_workgroup(blockIdx.x);      // the forward's mapping: the four blocks of a tile on one XCD
+    const int tile_local = tq.tile_local, quad = tq.quad;
     if (tile_local >= n_band_tiles) return;
-    const int tile = cam.tile_y0 * cam.gx + tile_local;
-    const int tx = tile % cam.gx, ty = tile / cam.gx;
+    const gsrb::Block8 blk(cam, tile_local, quad);
+    const int tile = blk.tile, tx = blk.tx, ty = blk.ty;
     const int lane = threadIdx.x;
-    const int bx0 = tx * GSR_TILE + (quad & 1) * 8, by0 = ty * GSR_TILE + (quad >> 1) * 8;
+    const int bx0 = blk.bx0, by0 = blk.by0;
     if (bx0 >= cam.W || by0 >= cam.H) return;
     const int px = bx0 + (lane & 7), py = by0 + (lane >> 3);
     const bool inside = px < cam.W && py < cam.H;
@@ -130,12 +85,12 @@ contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, 
         bool keep = false;
         uint32_t k_emit = 0;
         if ((uint32_t)lane < n) {
-            const float qmin = min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, x0, x1, y0, y1);
+            const float qmin = gsrb::min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, x0, x1, y0, y1);
             keep = !(qmin > q2.z);                 // q2.z = 2 ln(255 opacity) + 0.01, written by the preprocess
-            q0.z *= -0.5f * LOG2E;                  // conic -> log2 units, sign folded in (the forward's products)
-            q0.w *= -LOG2E;
-            q1.x *= -0.5f * LOG2E;
-            k_emit = emission_index(q3, (uint32_t)tx, (uint32_t)ty);
+            q0.z = gsrb::conic_diag_to_log2(q0.z);      // conic -> log2 units, sign folded in
+            q0.w = gsrb::conic_cross_to_log2(q0.w);
+            q1.x = gsrb::conic_diag_to_log2(q1.x);
+            k_emit = gsrb::emission_index(q3, (uint32_t)tx, (uint32_t)ty);
         }
         const uint64_t mask = __ballot(keep);
         if (keep) {
@@ -151,11 +106,10 @@ contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, 
             const float4 r0 = s_rec[u * 2 + 0];
             const float4 r1 = s_rec[u * 2 + 1];
             const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(r1.z), 0);      // (wave-uniform: the entry's lane of the batch, as a scalar)
-            // ---- blend_step_bf's expressions (mul, fma, fma; min; fma), so that alpha, the hard masks and T are the forward's bits ----
+            // ---- the forward's p2, alpha and testT (gsr_blend.h; blend_step_bf), so that the hard masks and T are the forward's bits ----
             const float dx = r0.x - pxf, dy = r0.y - pyf;
-            const float t = fmaf(r0.w, dy, r0.z * dx);
-            const float p2 = fmaf(dx, t, (r1.x * dy) * dy);           // log2(e) * power
-            const float alpha = fminf(GSR_ALPHA_MAX, r1.y * __builtin_amdgcn_exp2f(p2));
+            const float p2 = gsrb::p2(dx, dy, r0.z, r0.w, r1.x);           // log2(e) * power
+            const float alpha = gsrb::alpha(r1.y, p2);
             const bool contrib = (p2 <= 0.0f) & (alpha >= GSR_ALPHA_MIN) & (pos_base + j <= last);
             const float testT = fmaf(-alpha, Tl, Tl);                // T (1 - alpha)
             const float w = alpha * Tl;
@@ -163,14 +117,9 @@ contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, 
             const uint64_t hit = __ballot(contrib);
             if (hit == 0ull) continue;
             const float v = contrib ? E * w : 0.0f;
-            float s = v;
-            uint32_t m = __float_as_uint(fmaxf(v, 0.0f));
-            sum_max_stage<0x111>(s, m);   // row_shr:1
-            sum_max_stage<0x112>(s, m);   // row_shr:2
-            sum_max_stage<0x114>(s, m);   // row_shr:4
-            sum_max_stage<0x118>(s, m);   // row_shr:8
-            sum_max_stage<0x142>(s, m);   // row_bcast:15 (consumed in lanes 31 / 63)
-            sum_max_stage<0x143>(s, m);   // row_bcast:31 (consumed in lane 63)
+            float s;
+            uint32_t m;
+            gsrw::wave_sum_max_to_lane63(v, s, m);
             if (lane == 63) s_out[j] = make_float4(s, __uint_as_float(m), __uint_as_float((uint32_t)__popcll(hit)), 0.f);
             touched |= 1ull << j;
         }

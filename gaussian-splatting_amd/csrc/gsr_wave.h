@@ -1,4 +1,5 @@
-// wave64 / workgroup primitives shared by the binning and sorting kernels (device only).
+// wave64 / workgroup primitives shared by the binning, sorting and blend kernels (device only): integer DPP scans, workgroup scans, digit matching,
+// and the float DPP / permlane reductions of the blend backward and the contribution statistics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,6 +84,93 @@ __device__ __forceinline__ uint64_t match_digit(uint32_t digit, int bits, uint64
         hi = __builtin_amdgcn_bitop3_b32(hi, (uint32_t)(bal >> 32), (uint32_t)sx, 0x90);
     }
     return ((uint64_t)hi << 32) | lo;
+}
+
+// ------------------------------------------------------------------------------------------------
+// float reductions over the wave (blend backward, contribution statistics)
+// ------------------------------------------------------------------------------------------------
+#ifdef GSR_SIMT_SHIM      // (tests/simt/: the kernel source compiled for the host, where the two swap builtins are functions of the shim)
+typedef uint2 uint2v;
+#else
+typedef unsigned uint2v __attribute__((ext_vector_type(2)));
+#endif
+
+// Every cross-lane add of the walk is ONE v_add_f32_dpp: the DPP moves use the full row mask and bound_ctrl (a lane without a source reads 0; the rows a
+// partial row mask would protect only hold partial sums nobody reads: row_bcast:15 results are consumed in lanes 31 / 63, row_bcast:31 in lane 63), and
+// the sum is pinned in a register before the branch that consumes it.  (Rounds 2-4 left four of them per step as v_mov 0 + v_mov_dpp + v_add: the
+// compiler sinks the add of the last row_shr into the "(lane & 15) == 15" branch -- a DPP move cannot follow it there -- and it cannot fuse a move with a
+// partial row mask into a float add, the kept lanes would need -0 + 0 = -0.)  103 -> 95 VALU per step; the consumed lanes add the same values in the same
+// order, so the gradients are the bits of the earlier form (tests/test_simt_forward_cpu.py ran both); measured on the GPU, same box, interleaved:
+// blend backward 0.342 -> 0.326 ms (profiles/r05_ab_candidates.json).
+// dpp_pin: no instruction -- the sum exists in all lanes here, so its add stays next to its DPP move instead of sinking into the consumer's branch, and
+// the pins of one stage keep their order
+__device__ __forceinline__ void dpp_pin(float& r) {
+#if !defined(GSR_SIMT_SHIM)
+    asm volatile("" : "+v"(r));
+#endif
+}
+template <int CTRL, int ROW_MASK /*documents which rows consume the result; the move itself takes all rows*/>
+__device__ __forceinline__ float dpp_add(float v) {
+    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
+    return v + __int_as_float(moved);
+}
+// The maximum of NON-NEGATIVE floats, taken on their bit patterns: they order like their bits, +0 (what a lane without a source reads) is the smallest
+// of them, and an integer maximum needs no NaN canonicalisation of its operands -- one v_max_u32_dpp.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_max_bits(uint32_t m) {
+    return max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, CTRL, 0xf, 0xf, true));
+}
+
+// sum over the 64 lanes; the total is valid in lane 63 only
+__device__ __forceinline__ float wave_sum_to_lane63(float v) {
+    v = dpp_add<0x111, 0xf>(v);   // row_shr:1
+    v = dpp_add<0x112, 0xf>(v);   // row_shr:2
+    v = dpp_add<0x114, 0xf>(v);   // row_shr:4
+    v = dpp_add<0x118, 0xf>(v);   // row_shr:8
+    v = dpp_add<0x142, 0xa>(v);   // row_bcast:15 -> rows 1,3
+    v = dpp_add<0x143, 0xc>(v);   // row_bcast:31 -> rows 2,3
+    return v;
+}
+// The same chain and, stage by stage beside it, the maximum of the values clamped at 0 (as bits): s = sum(v), m = bits of max(0, max v), both valid in
+// lane 63 only.  A lane without a DPP source reads 0: the identity of the sum and of a maximum that is clamped at 0 by definition.
+__device__ __forceinline__ void wave_sum_max_to_lane63(float v, float& s, uint32_t& m) {
+    s = v;
+    m = __float_as_uint(fmaxf(v, 0.0f));
+#define GSR_STEP(C, M) s = dpp_add<C, M>(s); m = dpp_max_bits<C>(m);
+    GSR_DPP_SCAN_STEPS(GSR_STEP)
+#undef GSR_STEP
+}
+
+// [a.lo+a.hi | b.lo+b.hi] : lanes 0-31 hold 32 partial sums of a, lanes 32-63 of b
+__device__ __forceinline__ float fold32(float a, float b) {
+    const uint2v r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+// rows (16 lanes): [p.row0+p.row1 | q.row0+q.row1 | p.row2+p.row3 | q.row2+q.row3]
+__device__ __forceinline__ float fold16(float p, float q) {
+    const uint2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(q), false, false);
+    return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+// Four values summed over the wave at once.  Result: lane 15 -> sum(a), lane 31 -> sum(c), lane 47 -> sum(b),
+// lane 63 -> sum(d) (other lanes hold partial sums).
+__device__ __forceinline__ float reduce4(float a, float b, float c, float d) {
+    float v = fold16(fold32(a, b), fold32(c, d));
+    v = dpp_add<0x111, 0xf>(v);
+    v = dpp_add<0x112, 0xf>(v);
+    v = dpp_add<0x114, 0xf>(v);
+    v = dpp_add<0x118, 0xf>(v);
+    return v;
+}
+
+// Two values summed over the wave: lane 31 -> sum(a), lane 63 -> sum(b)
+__device__ __forceinline__ float reduce2(float a, float b) {
+    float v = fold32(a, b);
+    v = dpp_add<0x111, 0xf>(v);
+    v = dpp_add<0x112, 0xf>(v);
+    v = dpp_add<0x114, 0xf>(v);
+    v = dpp_add<0x118, 0xf>(v);
+    v = dpp_add<0x142, 0xa>(v);   // row_bcast:15 -> rows 1,3
+    return v;
 }
 
 }  // namespace gsrw

@@ -15,7 +15,7 @@
 //                      box test as the forward: a culled entry contributed to no pixel of the box, so its gradient from
 //                      this box is zero), park the batch in the wave's private LDS, then walk the survivors (s_flbit);
 //                      every lane computes its pixel's 10 per-pair values (five MOMENTS of the pixel offset, see
-//                      bwd_step, plus opacity / colour / inverse-depth terms), and the 10 values are summed over the 64
+//                      moments_to_grads, plus opacity / colour / inverse-depth terms), and the 10 values are summed over the 64
 //                      lanes with a transpose-reduce: v_permlane32_swap + v_permlane16_swap butterflies fold four values
 //                      into one register (one value per 16-lane row), DPP row shifts finish each row -- ~27 VALU ops for
 //                      10 values instead of 60.  Lanes 15/31/47/63 store the row totals into the batch's LDS record
@@ -35,51 +35,22 @@
 // (sum m dx, sum m dy, sum m dx^2, sum m dx dy, sum m dy^2) in slots 0..4 instead.
 #include "gsr_internal.h"
 #include <algorithm>
+#include "gsr_blend.h"
 #include "gsr_wave.h"
 
 namespace {
 
-#ifdef GSR_SIMT_SHIM      // (tests/simt/: the kernel source compiled for the host, where the two swap builtins are functions of the shim)
-typedef uint2 uint2v;
-#else
-typedef unsigned uint2v __attribute__((ext_vector_type(2)));
-#endif
+using gsrw::dpp_add;
+using gsrw::dpp_pin;
+using gsrw::fold16;
+using gsrw::fold32;
 
-// Every cross-lane add of the walk is ONE v_add_f32_dpp: the DPP moves use the full row mask and bound_ctrl (a lane without a source reads 0; the rows a
-// partial row mask would protect only hold partial sums nobody reads: row_bcast:15 results are consumed in lanes 31 / 63, row_bcast:31 in lane 63), and
-// the sum is pinned in a register before the branch that consumes it.  (Rounds 2-4 left four of them per step as v_mov 0 + v_mov_dpp + v_add: the
-// compiler sinks the add of the last row_shr into the "(lane & 15) == 15" branch -- a DPP move cannot follow it there -- and it cannot fuse a move with a
-// partial row mask into a float add, the kept lanes would need -0 + 0 = -0.)  103 -> 95 VALU per step; the consumed lanes add the same values in the same
-// order, so the gradients are the bits of the earlier form (tests/test_simt_forward_cpu.py ran both); measured on the GPU, same box, interleaved:
-// blend backward 0.342 -> 0.326 ms (profiles/r05_ab_candidates.json).
-// dpp_pin: no instruction -- the sum exists in all lanes here, so its add stays next to its DPP move instead of sinking into the consumer's branch, and
-// the pins of one stage keep their order
-__device__ __forceinline__ void dpp_pin(float& r) {
-#if !defined(GSR_SIMT_SHIM)
-    asm volatile("" : "+v"(r));
-#endif
-}
-template <int CTRL, int ROW_MASK /*documents which rows consume the result; the move itself takes all rows*/>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true);
-    return v + __int_as_float(moved);
-}
+// one stage of the walk's three reduction chains (dpp_add / dpp_pin: gsr_wave.h)
 template <int CTRL>
 __device__ __forceinline__ void dpp_stage(float& c, float& a, float& b) {
     c = dpp_add<CTRL, 0xf>(c); dpp_pin(c);
     a = dpp_add<CTRL, 0xf>(a); dpp_pin(a);
     b = dpp_add<CTRL, 0xf>(b); dpp_pin(b);
-}
-
-// sum over the 64 lanes; the total is valid in lane 63 only
-__device__ __forceinline__ float wave_sum_to_lane63(float v) {
-    v = dpp_add<0x111, 0xf>(v);   // row_shr:1
-    v = dpp_add<0x112, 0xf>(v);   // row_shr:2
-    v = dpp_add<0x114, 0xf>(v);   // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);   // row_shr:8
-    v = dpp_add<0x142, 0xa>(v);   // row_bcast:15 -> rows 1,3
-    v = dpp_add<0x143, 0xc>(v);   // row_bcast:31 -> rows 2,3
-    return v;
 }
 
 // one step of a segmented inclusive scan over the wave: lanes whose DPP source lane carries the same segment id add its values
@@ -94,71 +65,8 @@ __device__ __forceinline__ void seg_scan_step(int seg, float (&v)[10]) {
     }
 }
 
-// [a.lo+a.hi | b.lo+b.hi] : lanes 0-31 hold 32 partial sums of a, lanes 32-63 of b
-__device__ __forceinline__ float fold32(float a, float b) {
-    const uint2v r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-// rows (16 lanes): [p.row0+p.row1 | q.row0+q.row1 | p.row2+p.row3 | q.row2+q.row3]
-__device__ __forceinline__ float fold16(float p, float q) {
-    const uint2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(q), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-// Four values summed over the wave at once.  Result: lane 15 -> sum(a), lane 31 -> sum(c), lane 47 -> sum(b),
-// lane 63 -> sum(d) (other lanes hold partial sums).
-__device__ __forceinline__ float reduce4(float a, float b, float c, float d) {
-    float v = fold16(fold32(a, b), fold32(c, d));
-    v = dpp_add<0x111, 0xf>(v);
-    v = dpp_add<0x112, 0xf>(v);
-    v = dpp_add<0x114, 0xf>(v);
-    v = dpp_add<0x118, 0xf>(v);
-    return v;
-}
-
-// Two values summed over the wave: lane 31 -> sum(a), lane 63 -> sum(b)
-__device__ __forceinline__ float reduce2(float a, float b) {
-    float v = fold32(a, b);
-    v = dpp_add<0x111, 0xf>(v);
-    v = dpp_add<0x112, 0xf>(v);
-    v = dpp_add<0x114, 0xf>(v);
-    v = dpp_add<0x118, 0xf>(v);
-    v = dpp_add<0x142, 0xa>(v);   // row_bcast:15 -> rows 1,3
-    return v;
-}
-
-__device__ __forceinline__ float min_q_over_box(float mx, float my, float A, float B, float C, float x0, float x1,
-                                                float y0, float y1) {
-    const float lx = x0 - mx, hx = x1 - mx, ly = y0 - my, hy = y1 - my;
-    const bool in_x = (lx <= 0.0f) && (hx >= 0.0f);
-    const bool in_y = (ly <= 0.0f) && (hy >= 0.0f);
-    float q = 3.0e38f;
-    if (in_x && in_y) return 0.0f;
-    if (!in_x) {
-        const float dx = lx > 0.0f ? lx : hx;
-        const float dy = fminf(hy, fmaxf(ly, -B * dx * __builtin_amdgcn_rcpf(C)));
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    if (!in_y) {
-        const float dy = ly > 0.0f ? ly : hy;
-        const float dx = fminf(hx, fmaxf(lx, -B * dy * __builtin_amdgcn_rcpf(A)));
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    return q;
-}
-
-__device__ __forceinline__ float bcast(float v, int srclane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srclane));
-}
-
-// per-pixel running state of the back-to-front walk (Appendix A.5).  The reference keeps one running colour per channel
-// ("accum_rec") and dots (c - accum) with dL/dpixel afterwards; both are linear in the channel, so the walk here carries
-// the already-dotted scalars: accD = <accum, dL/dpix>, lastD = <last colour, dL/dpix> -- 2 VALU ops per step instead of 12.
-struct BwdPix {
-    float T, accD, lastD, last_alpha;
-};
-
-// One (pixel, Gaussian) step.  Outputs are zero when the pixel does not take part (hard masks: behind n_contrib,
-// power > 0, alpha < 1/255).  The five geometric outputs are the raw MOMENTS of m = dL/dG * G over the pixel offsets,
+// What a (pixel, Gaussian) step of the walk yields is zero when the pixel does not take part (hard masks: behind n_contrib,
+// power > 0, alpha < 1/255).  Its five geometric values are the raw MOMENTS of m = dL/dG * G over the pixel offsets,
 //     mx = m dx, my = m dy, mxx = m dx^2, mxy = m dx dy, myy = m dy^2,
 // not the derivatives themselves: the derivatives are linear in the moments with per-Gaussian coefficients
 //     dL/dpx = -A mx - B my,  dL/dpy = -C my - B mx,  dL/dA = -mxx/2,  dL/dB = -mxy,  dL/dC = -myy/2
@@ -174,43 +82,6 @@ __device__ __forceinline__ v2f operator*(v2f a, v2f b) { return {a.x * b.x, a.y 
 __device__ __forceinline__ v2f operator*(float a, v2f b) { return {a * b.x, a * b.y}; }
 __device__ __forceinline__ v2f operator-(v2f a) { return {-a.x, -a.y}; }
 
-__device__ __forceinline__ bool bwd_step(BwdPix& s, bool take, float pxf, float pyf, float Tf_bg, float dLr, float dLg,
-                                         float dLb, float dLd, float gx_, float gy_, float a2, float b2, float c2, float op,
-                                         float cr, float cg, float cb, float idp, float& mx, float& my, float& mxx,
-                                         float& mxy, float& myy, float& g_op, float& g_r, float& g_g, float& g_b,
-                                         float& g_d) {
-    const v2f d = (v2f){gx_, gy_} - (v2f){pxf, pyf};
-    const float dx = d.x, dy = d.y;
-    const float t = fmaf(b2, dy, a2 * dx);
-    const float p2 = fmaf(dx, t, (c2 * dy) * dy);
-    const float G = __builtin_amdgcn_exp2f(p2);
-    const float alpha = fminf(GSR_ALPHA_MAX, op * G);
-    const bool active = take & (p2 <= 0.0f) & (alpha >= GSR_ALPHA_MIN);
-    const v2f dL01 = {dLr, dLg}, dL23 = {dLb, dLd};
-    const v2f cd = (v2f){cr, cg} * dL01 + (v2f){cb, idp} * dL23;
-    const float cD = cd.x + cd.y;
-    float w = 0.0f, dL_dalpha = 0.0f;
-    if (active) {
-        const float inv1ma = __builtin_amdgcn_rcpf(1.0f - alpha);
-        s.T = s.T * inv1ma;
-        w = alpha * s.T;
-        s.accD = fmaf(s.last_alpha, s.lastD - s.accD, s.accD);
-        s.lastD = cD;
-        s.last_alpha = alpha;
-        dL_dalpha = fmaf(cD - s.accD, s.T, Tf_bg * inv1ma);      // Tf_bg = -T_final * <bg, dL/dpix>
-    }
-    const v2f g01 = w * dL01, g23 = w * dL23;
-    g_r = g01.x; g_g = g01.y; g_b = g23.x; g_d = g23.y;
-    const float m = op * (G * dL_dalpha);
-    g_op = m;                            // zeroth moment (see moments_to_grads)
-    const v2f md = m * d;                // (m dx, m dy)
-    const v2f mxd = md.x * d;            // (m dx^2, m dx dy)
-    mx = md.x; my = md.y;
-    mxx = mxd.x; mxy = mxd.y;
-    myy = md.y * dy;
-    return active;
-}
-
 // per-Gaussian conversion of the summed moments into the derivatives (record layout of the file header)
 // Slot 5 of an instance record carries the ZEROTH moment sum(m) = opacity * sum(G dL/dalpha) (round 3: the blend kernel needs m
 // anyway, so dL/dopacity = sum(m) / opacity is one division per Gaussian here instead of two multiplies and an add per step there;
@@ -225,14 +96,6 @@ __device__ __forceinline__ void moments_to_grads(float A, float B, float C, floa
     u1.y = opacity > 0.0f ? u1.y / opacity : 0.0f;
 }
 
-constexpr float LOG2E = 1.4426950408889634f;
-
-// q3 of the splat record = (rect.x bits, rect.y bits, first emission index bits, tiles bits), see preprocess.hip / binning.hip
-__device__ __forceinline__ uint32_t emission_index(const float4 q3, uint32_t tx, uint32_t ty) {
-    const uint32_t rx = __float_as_uint(q3.x), ry = __float_as_uint(q3.y), goff = __float_as_uint(q3.z);
-    const uint32_t minx = rx & 0xFFFFu, w = (rx >> 16) - minx, miny = ry & 0xFFFFu;
-    return goff + (ty - miny) * w + (tx - minx);
-}
 constexpr int REC_STRIDE = 3;      // float4 per staged entry (48 B: 12-word stride, 3 coprime to 16 -> per-lane ds_read_b128 is conflict-free)
 
 // ------------------------------------------------------------------------------------------------
@@ -372,11 +235,11 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
         if ((uint32_t)lane < n) {
             const uint32_t pos = base + (uint32_t)lane;
             // an entry at or behind a quadrant's own last contributor touches none of its pixels
-            keepA = pos < mxA && !(min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, xa0, xa1, y0, y1) > q2.z);
-            keepB = quadB_alive && pos < mxB && !(min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, xb0, xb1, y0, y1) > q2.z);
-            k_emit = emission_index(q3, (uint32_t)tx, (uint32_t)ty);
-            s_rec[lane * REC_STRIDE + 0] = make_float4(q0.x, q0.y, -0.5f * LOG2E * q0.z, -LOG2E * q0.w);
-            s_rec[lane * REC_STRIDE + 1] = make_float4(-0.5f * LOG2E * q1.x, q1.y, q1.z, q1.w);
+            keepA = pos < mxA && !(gsrb::min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, xa0, xa1, y0, y1) > q2.z);
+            keepB = quadB_alive && pos < mxB && !(gsrb::min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, xb0, xb1, y0, y1) > q2.z);
+            k_emit = gsrb::emission_index(q3, (uint32_t)tx, (uint32_t)ty);
+            s_rec[lane * REC_STRIDE + 0] = make_float4(q0.x, q0.y, gsrb::conic_diag_to_log2(q0.z), gsrb::conic_cross_to_log2(q0.w));
+            s_rec[lane * REC_STRIDE + 1] = make_float4(gsrb::conic_diag_to_log2(q1.x), q1.y, q1.z, q1.w);
             s_rec[lane * REC_STRIDE + 2] = make_float4(q2.x, q2.w, 0.f, 0.f);
         }
         const uint64_t maskA = __ballot(keepA), maskB = __ballot(keepB);
@@ -395,16 +258,15 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
             if (HAS_DEPTH) { const float2 r2 = *reinterpret_cast<const float2*>(&s_rec[j * REC_STRIDE + 2]); r2x = r2.x; r2y = r2.y; }
             else r2x = s_rec[j * REC_STRIDE + 2].x;
             const float a2 = r0.z, b2 = r0.w, c2 = r1.x, op = r1.y;
-            // ---- geometry: the forward's operation sequence per pixel (mul, fma, fma; blend_step_bf in render_fwd.hip), so
-            // that the hard masks agree with the forward's bit for bit ----
+            // ---- geometry: the forward's operation sequence per pixel (gsr_blend.h: p2 for the lane's two pixels, which share the square
+            // term), so that the hard masks agree with the forward's bit for bit ----
             const float dxA = r0.x - pxfA, dxB = r0.x - pxfB;
             const float dy = r0.y - pyf;
-            const float u = (c2 * dy) * dy;
-            const float tA = fmaf(b2, dy, a2 * dxA), tB = fmaf(b2, dy, a2 * dxB);
-            const float p2A = fmaf(dxA, tA, u), p2B = fmaf(dxB, tB, u);
+            float p2A, p2B;
+            gsrb::p2_pair(dxA, dxB, dy, a2, b2, c2, p2A, p2B);
             const float GA = __builtin_amdgcn_exp2f(p2A), GB = __builtin_amdgcn_exp2f(p2B);
-            const float ogA = op * GA, ogB = op * GB;
-            const float alA = fminf(GSR_ALPHA_MAX, ogA), alB = fminf(GSR_ALPHA_MAX, ogB);
+            const float ogA = op * GA, ogB = op * GB;      // (opacity * G is needed beside alpha: gsrb::alpha_of, not gsrb::alpha)
+            const float alA = gsrb::alpha_of(ogA), alB = gsrb::alpha_of(ogB);
             const bool actA = doA & (pos0 < lastA) & (p2A <= 0.0f) & (alA >= GSR_ALPHA_MIN);
             const bool actB = doB & (pos0 < lastB) & (p2B <= 0.0f) & (alB >= GSR_ALPHA_MIN);
             if (__builtin_amdgcn_ballot_w64(actA | actB) == 0ull) continue;
@@ -430,7 +292,7 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
             const float msum = m.x + m.y, mdxsum = mdx.x + mdx.y;
             const float g_px = mdxsum, g_py = msum * dy, g_A = mdxx.x + mdxx.y, g_B = mdxsum * dy, g_C = (msum * dy) * dy;
             const float g_op = msum, g_r = gr2.x + gr2.y, g_g = gg2.x + gg2.y, g_b = gb2.x + gb2.y;      // g_op: the zeroth moment
-            // the three reductions stage by stage (same adds per chain as reduce4 / reduce2 / wave_sum_to_lane63 above, which the measurement build's variants still call): between two DPP adds of one chain
+            // the three reductions stage by stage (same adds per chain as reduce4 / reduce2 / wave_sum_to_lane63 of gsr_wave.h, which the measurement build's variants still call): between two DPP adds of one chain
             // stand the other two chains' adds -- the two wait states a DPP read of a fresh VALU result needs, filled with work instead of s_nop
             float v0 = fold16(fold32(g_px, g_A), fold32(g_py, g_B));     // -> slots 0,1,2,3
             float v1 = fold16(fold32(g_C, g_r), fold32(g_op, g_g));      // -> slots 4,5,6,7
@@ -481,8 +343,10 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
     }
 }
 
-#ifdef GSR_AB_VARIANTS
-#include "render_bwd_quad_superbatch.inc"      // measured-and-rejected variants (tools/ab_variants/): measurement build only
+#ifdef GSR_AB_VARIANTS      // measured-and-rejected variants (tools/ab_variants/): measurement build only
+#include "render_bwd_step.inc"                 // their common per-pixel step
+#include "render_bwd_quad_superbatch.inc"
+#include "render_bwd_atomics.inc"
 #endif  // GSR_AB_VARIANTS
 
 // splat_grads[g] = sum of the instance records of Gaussian g.  In emission (= depth) order a Gaussian's records are one
@@ -739,10 +603,6 @@ reduce_stitch(int64_t nunits, const uint32_t* __restrict__ order, const float4* 
     }
     finish_row(order, splats, splat_grads, j, v);
 }
-
-#ifdef GSR_AB_VARIANTS
-#include "render_bwd_atomics.inc"      // measured-and-rejected variants (tools/ab_variants/): measurement build only
-#endif  // GSR_AB_VARIANTS
 
 // ------------------------------------------------------------------------------------------------
 // Heaviest tiles first.  A wave of the blend backward lives for a third of the kernel, the heaviest does 1.8-2x the mean

@@ -26,39 +26,13 @@
 // <= 1e-5 except at pixels where a hard threshold (alpha<1/255, T<1e-4, power>0) is within rounding noise
 // (tests/ use the oracle's "fragile" mask for those).
 #include "gsr_internal.h"
+#include "gsr_blend.h"
 
 namespace {
 
 #ifdef GSR_AB_VARIANTS
 #include "render_fwd_block.inc"      // measured-and-rejected variants (tools/ab_variants/): measurement build only
 #endif  // GSR_AB_VARIANTS
-
-// ------------------------------------------------------------------------------------------------
-// wave per 8x8 pixel block: helpers (exact box test, cross-lane broadcast)
-// ------------------------------------------------------------------------------------------------
-// Smallest value of q(d) = A dx^2 + 2 B dx dy + C dy^2 over the pixel box [x0,x1]x[y0,y1] for a Gaussian centred
-// at (mx,my).  Exact for positive-definite (A,B,C): the minimiser is the centre if it is inside, otherwise it
-// lies on an edge facing the centre, where q restricted to the edge is a 1-D parabola with a clamped optimum.
-__device__ __forceinline__ float min_q_over_box(float mx, float my, float A, float B, float C, float x0, float x1,
-                                                float y0, float y1) {
-    const float lx = x0 - mx, hx = x1 - mx, ly = y0 - my, hy = y1 - my;   // box in centre-relative coords
-    const bool in_x = (lx <= 0.0f) && (hx >= 0.0f);
-    const bool in_y = (ly <= 0.0f) && (hy >= 0.0f);
-    float q = 3.0e38f;
-    if (in_x && in_y) return 0.0f;
-    if (!in_x) {
-        const float dx = lx > 0.0f ? lx : hx;                 // facing vertical edge
-        const float dy = fminf(hy, fmaxf(ly, -B * dx * __builtin_amdgcn_rcpf(C)));   // clamped optimum along it (tau carries a 0.01 margin: v_rcp_f32's ulp is harmless)
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    if (!in_y) {
-        const float dy = ly > 0.0f ? ly : hy;
-        const float dx = fminf(hx, fmaxf(lx, -B * dy * __builtin_amdgcn_rcpf(A)));
-        q = fminf(q, A * dx * dx + 2.0f * B * dx * dy + C * dy * dy);
-    }
-    return q;
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // variants 0 / 3: wave per 8x8 pixel block with a BRANCH-FREE blend body.
@@ -90,9 +64,8 @@ __device__ __forceinline__ void blend_step_bf(PixAcc& s, float& Tl, float pxf, f
                                               float b2, float c2, float op, float r, float g, float b, float invd,
                                               uint32_t pos) {
     const float dx = gx_ - pxf, dy = gy_ - pyf;
-    const float t = fmaf(b2, dy, a2 * dx);
-    const float p2 = fmaf(dx, t, (c2 * dy) * dy);           // log2(e) * power
-    const float alpha = fminf(GSR_ALPHA_MAX, op * __builtin_amdgcn_exp2f(p2));
+    const float p2 = gsrb::p2(dx, dy, a2, b2, c2);           // log2(e) * power
+    const float alpha = gsrb::alpha(op, p2);
     const bool valid = (p2 <= 0.0f) & (alpha >= GSR_ALPHA_MIN);
     const float testT = fmaf(-alpha, Tl, Tl);                // T (1 - alpha)
     const bool term = valid & (testT < GSR_T_EPS);
@@ -122,12 +95,9 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
     float4* s_rec = s_rec_all + (USE_LDS ? (threadIdx.x >> 6) * 64 * 3 : 0);
     int tile_local, quad;
     if (WPB == 1) {
-        // XCD-aware mapping: workgroup b runs on XCD b % 8 (observed).  The four 8x8 blocks of a tile share one splat
-        // list, so they get ids b, b+8, b+16, b+24 -> same XCD -> same L2.
-        const int b = blockIdx.x;
-        const int grp = b >> 5, r32 = b & 31;
-        tile_local = tile_off + grp * 8 + (r32 & 7);
-        quad = r32 >> 3;
+        const gsrb::TileQuad tq = gsrb::block8_of_workgroup(blockIdx.x);
+        tile_local = tq.tile_local + tile_off;
+        quad = tq.quad;
     } else {
         tile_local = tile_off + blockIdx.x;
         quad = threadIdx.x >> 6;
@@ -136,10 +106,10 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
     const unsigned long long t_start = counters ? wall_clock64() : 0ull;      // (measurement only: per-wave trace, gsr_profile_trace)
     const bool tracing = counters && gsr_trace_mode(counters);
     unsigned long long t_mark = t_start, t_walk = 0ull, t_prep = 0ull;
-    const int tile = cam.tile_y0 * cam.gx + tile_local;
-    const int tx = tile % cam.gx, ty = tile / cam.gx;
+    const gsrb::Block8 blk(cam, tile_local, quad);
+    const int tile = blk.tile;
     const int lane = threadIdx.x & 63;
-    const int bx0 = tx * GSR_TILE + (quad & 1) * 8, by0 = ty * GSR_TILE + (quad >> 1) * 8;
+    const int bx0 = blk.bx0, by0 = blk.by0;
     if (bx0 >= cam.W || by0 >= cam.H) {
         if (TRACK && lane == 0) block_steps[tile * 4 + quad] = 0u;
         return;
@@ -152,7 +122,6 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
     const uint2 range = ranges[tile];
     PixAcc s = {1.0f, 0.f, 0.f, 0.f, 0.f, 0u};
     float Tl = inside ? 1.0f : 0.0f;          // live transmittance (0 = this lane takes no further entries)
-    constexpr float LOG2E = 1.4426950408889634f;
 
     // Software pipeline over the batches of 64 list entries: every batch needs two dependent global loads (list id ->
     // 64-byte record gather), ~1-2 us under load, while a wave walks only a handful of batches before its pixels
@@ -176,11 +145,11 @@ render_fwd_wave_bf(GsrCamDev cam, int tile_off, int n_band_tiles /*tiles [tile_o
         if ((uint32_t)lane < n) {
             colb = q2.x;
             invd = q2.w;
-            const float qmin = min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, x0, x1, y0, y1);
+            const float qmin = gsrb::min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, x0, x1, y0, y1);
             keep = !(qmin > q2.z);                 // q2.z = 2 ln(255 opacity) + 0.01, written by the preprocess
-            q0.z *= -0.5f * LOG2E;                  // conic -> log2 units, sign folded in
-            q0.w *= -LOG2E;
-            q1.x *= -0.5f * LOG2E;
+            q0.z = gsrb::conic_diag_to_log2(q0.z);      // conic -> log2 units, sign folded in
+            q0.w = gsrb::conic_cross_to_log2(q0.w);
+            q1.x = gsrb::conic_diag_to_log2(q1.x);
         }
         // The survivors are parked COMPACTED, in list order (slot = survivors on lower lanes), with their list position in the record's spare
         // word.  The walk reads consecutive records -- constant ds_read offsets from one base register inside the eight-deep unrolled body, a

@@ -13,9 +13,7 @@
 #include "sort.hip"
 #include "route.hip"
 #include "render_fwd.hip"
-namespace tu_bwd {      // (render_fwd.hip and render_bwd.hip both define min_q_over_box / bcast in their anonymous namespaces)
 #include "render_bwd.hip"
-}  // namespace tu_bwd
 #include "simt_runtime.h"
 #include <vector>
 
@@ -100,15 +98,15 @@ int64_t simt_forward(const GsrRasterSettings* s, int snug, int P, int M, const f
                               out_color, out_invdepth, 0, nullptr, nullptr);
     if (simt::launch_error) return bail();
     if (dL_dcolor && track) {
-        const size_t nr = (size_t)(R > 0 ? R : 1), nu = tu_bwd::gsr_reduce_units((int64_t)nr);
+        const size_t nr = (size_t)(R > 0 ? R : 1), nu = gsr_reduce_units((int64_t)nr);
         std::vector<float> splat_grads((size_t)P * 12 + 16, 0.f), inst_grads(nr * 12 * GSR_BWD_SLOTS + 16), unit_piece(nu * 24 + 32);
         std::vector<uint32_t> inst_flag(nr + 16), tile_order((size_t)n_tiles * 2 + 16);
         std::vector<uint2> unit_first(nu + 16);
         if (R > 0) {
-            tu_bwd::gsr_launch_render_backward(c, ranges, point_list, g.splats, final_T, n_contrib, block_steps.data(), tile_order.data(), dL_dcolor, dL_dinvdepth,
+            gsr_launch_render_backward(c, ranges, point_list, g.splats, final_T, n_contrib, block_steps.data(), tile_order.data(), dL_dcolor, dL_dinvdepth,
                                                nullptr, inst_grads.data(), inst_flag.data(), (int64_t)R, 0, 2, nullptr, nullptr);
             if (simt::launch_error) return bail();
-            tu_bwd::gsr_launch_reduce_instances(P, (int64_t)R, g.vals[1], g.offsets, g.splats, inst_grads.data(), inst_flag.data(), splat_grads.data(),
+            gsr_launch_reduce_instances(P, (int64_t)R, g.vals[1], g.offsets, g.splats, inst_grads.data(), inst_flag.data(), splat_grads.data(),
                                                 unit_first.data(), unit_piece.data(), nullptr);
             if (simt::launch_error) return bail();
         }

@@ -1,20 +1,30 @@
 // Self-test of the SIMT-on-CPU shim (tests/test_simt_shim_cpu.py): the wave-level primitives the csrc/ kernels are written in, run on the
 // shim and compared with plain loops -- DPP scans (row_shr / row_bcast / wave_shr / wave_shl), ballots and digit matching, workgroup scans,
-// the cross-lane reductions of the blend backward (DPP + permlane swaps), readlane, __shfl_xor, and the case that once went wrong: a lane
+// the cross-lane reductions of the blend backward and of the contribution statistics (DPP + permlane swaps; gsr_wave.h), readlane, __shfl_xor, and the case that once went wrong: a lane
 // that LEAVES the kernel right after a wave-level operation must not take its value away from lanes that have not read it yet.
 #define __HIPCC__ 1
 #include "hip/hip_runtime.h"
 #include <stdio.h>
+#include <string.h>
 #include "gsr_wave.h"
-namespace tu_bwd {
-#include "render_bwd.hip"
-}
 #include "simt_runtime.h"
 using namespace gsrw;
 
 static uint32_t o_scan[256], o_max[256], o_excl[256], o_shr[256], o_shl[256], o_xor[256];
 static uint64_t o_bal[256], o_match[256], o_scan64[256];
-static float o_r2[256], o_r4[256], o_s63[256], o_rl[256][10];
+static float o_r2[256], o_r4[256], o_s63[256], o_rl[256][10], o_sm_s[256];
+static uint32_t o_sm_m[256];
+
+// input of the sum + maximum stage (wave_sum_max_to_lane63): mixed signs, both zeros, magnitudes over six decades, the 16-lane rows scaled
+// differently and rows 1 and 3 mirrored -- the total's bits differ between the DPP order, a lane-by-lane sum and other orders of the rows
+static float sum_max_input(int lane) {
+    if (lane % 11 == 3) return -0.0f;
+    if (lane % 11 == 7) return 0.0f;
+    const float row_scale[4] = {0.7f, 1.9f, 1.3f, 0.37f};
+    const float mag = ((float)(1 + (lane * 29) % 64) * (lane % 3 == 0 ? 1.0e-3f : lane % 3 == 1 ? 1.0f : 3.0e2f) + 1.0f / (float)(lane + 3)) * row_scale[lane >> 4];
+    const bool neg = ((lane * 7) % 5 < 2) != ((lane >> 4) % 2 == 1);
+    return neg ? -mag : mag;
+}
 
 static void kern() {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -30,9 +40,10 @@ static void kern() {
     uint32_t v[1] = {(uint32_t)(tid % 7)};
     o_excl[tid] = block_excl_scan<1>(v, wsum, lane, w);
     const float a = (float)(lane + 1), b = (float)(1000 + 2 * lane), c = (float)(lane * lane), d = 0.5f * lane;
-    o_r2[tid] = tu_bwd::reduce2(a, b);
-    o_r4[tid] = tu_bwd::reduce4(a, b, c, d);
-    o_s63[tid] = tu_bwd::wave_sum_to_lane63(a);
+    o_r2[tid] = reduce2(a, b);
+    o_r4[tid] = reduce4(a, b, c, d);
+    o_s63[tid] = wave_sum_to_lane63(a);
+    wave_sum_max_to_lane63(sum_max_input(lane), o_sm_s[tid], o_sm_m[tid]);
     float x[10];
     for (int i = 0; i < 10; ++i) x[i] = (float)(lane * 100 + i) * 0.5f;
     for (int i = 0; i < 10; ++i) o_rl[tid][i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[i]), 63));      // ... and the kernel ends here
@@ -45,8 +56,25 @@ extern "C" int simt_selftest(void) {
     uint32_t run = 0;
     float sa = 0, sb = 0, sc = 0, sd = 0;
     for (int l = 0; l < 64; ++l) { sa += l + 1; sb += 1000 + 2 * l; sc += l * l; sd += 0.5f * l; }
+    // the sum in the DPP association order: per 16-lane row the row_shr 1 / 2 / 4 / 8 tree into the row's last lane, then row_bcast:15 and
+    // row_bcast:31 -> (row3 + row2) + (row1 + row0); the maximum of the values clamped at 0, as bits
+    float row[4][16], vmax = 0.0f;
+    for (int l = 0; l < 64; ++l) {
+        const float v = sum_max_input(l);
+        row[l >> 4][l & 15] = v;
+        if (v > vmax) vmax = v;
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int sh = 1; sh < 16; sh *= 2)
+            for (int i = 15; i >= sh; --i) row[r][i] = row[r][i] + row[r][i - sh];
+    const float sm_sum = (row[3][15] + row[2][15]) + (row[1][15] + row[0][15]);
+    uint32_t sm_max, sm_sum_bits;
+    memcpy(&sm_max, &vmax, 4);
+    memcpy(&sm_sum_bits, &sm_sum, 4);
     for (int t = 0; t < 256; ++t) {
         const int lane = t & 63;
+        if (lane == 63 && __float_as_uint(o_sm_s[t]) != sm_sum_bits) fail("wave_sum_max_to_lane63 sum", t);
+        if (lane == 63 && o_sm_m[t] != sm_max) fail("wave_sum_max_to_lane63 max", t);
         if (o_scan[t] != (uint32_t)((lane + 1) * (lane + 2) / 2)) fail("wave_incl_scan_u32", t);
         if (o_scan64[t] != (uint64_t)(lane + 1) * 0x100000000ull + (uint64_t)(lane * (lane + 1) / 2)) fail("wave_incl_scan_u64", t);
         uint32_t m = 0; for (int l = 0; l <= lane; ++l) m = std::max(m, (uint32_t)((l * 37) % 64));

@@ -66,7 +66,7 @@ render_bwd_wave(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
             const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)id, j);
             float g_px, g_py, g_A, g_B, g_C, g_op, g_r, g_g, g_b, g_d;
             const bool active = bwd_step(s, pos0 < last_contrib, pxf, pyf, Tf_bg, dLr, dLg, dLb, dLd, gx_, gy_,
-                                         -0.5f * LOG2E * cA, -LOG2E * cB, -0.5f * LOG2E * cC, op, cr, cg, cb, idp, g_px, g_py,
+                                         gsrb::conic_diag_to_log2(cA), gsrb::conic_cross_to_log2(cB), gsrb::conic_diag_to_log2(cC), op, cr, cg, cb, idp, g_px, g_py,
                                          g_A, g_B, g_C, g_op, g_r, g_g, g_b, g_d);
             if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;
             g_px = wave_sum_to_lane63(g_px); g_py = wave_sum_to_lane63(g_py);

@@ -72,8 +72,8 @@ render_bwd_quad(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
             keep = !(min_q_over_box(q0.x, q0.y, q0.z, q0.w, q1.x, x0, x1, y0, y1) > q2.z);     // q2.z = tau
             k_emit = emission_index(q3, (uint32_t)tx, (uint32_t)ty);
             // staged entry with the log2-scaled conic: a2 = -0.5 log2(e) A, b2 = -log2(e) B, c2 = -0.5 log2(e) C
-            s_rec[lane * REC_STRIDE + 0] = make_float4(q0.x, q0.y, -0.5f * LOG2E * q0.z, -LOG2E * q0.w);
-            s_rec[lane * REC_STRIDE + 1] = make_float4(-0.5f * LOG2E * q1.x, q1.y, q1.z, q1.w);
+            s_rec[lane * REC_STRIDE + 0] = make_float4(q0.x, q0.y, gsrb::conic_diag_to_log2(q0.z), gsrb::conic_cross_to_log2(q0.w));
+            s_rec[lane * REC_STRIDE + 1] = make_float4(gsrb::conic_diag_to_log2(q1.x), q1.y, q1.z, q1.w);
             s_rec[lane * REC_STRIDE + 2] = make_float4(q2.x, q2.w, 0.f, 0.f);
         }
         uint64_t mask = __ballot(keep);
@@ -188,8 +188,8 @@ render_bwd_tile(GsrCamDev cam, const uint2* __restrict__ ranges, const uint32_t*
             const float4 q2 = splats[id * 4 +2];
             // staged entry: (x, y, a2, b2 | c2, opacity, r, g | b, 1/depth, tau, -) with the log2-scaled conic
             // a2 = -0.5 log2(e) A, b2 = -log2(e) B, c2 = -0.5 log2(e) C (power in base 2 = a2 dx^2 + b2 dx dy + c2 dy^2)
-            s_rec[tid * REC_STRIDE + 0] = make_float4(q0.x, q0.y, -0.5f * LOG2E * q0.z, -LOG2E * q0.w);
-            s_rec[tid * REC_STRIDE + 1] = make_float4(-0.5f * LOG2E * q1.x, q1.y, q1.z, q1.w);
+            s_rec[tid * REC_STRIDE + 0] = make_float4(q0.x, q0.y, gsrb::conic_diag_to_log2(q0.z), gsrb::conic_cross_to_log2(q0.w));
+            s_rec[tid * REC_STRIDE + 1] = make_float4(gsrb::conic_diag_to_log2(q1.x), q1.y, q1.z, q1.w);
             s_rec[tid * REC_STRIDE + 2] = make_float4(q2.x, q2.w, q2.z, 0.f);
             s_k[tid] = emission_index(splats[id * 4 + 3], (uint32_t)tx, (uint32_t)ty);
         }

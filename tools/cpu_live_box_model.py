@@ -39,7 +39,7 @@ plist = bins["point_list"].numpy()
 
 
 def min_q(mx, my, A, B, C, x0, x1, y0, y1):
-    """csrc/render_fwd.hip min_q_over_box, vectorised over entries."""
+    """csrc/gsr_blend.h min_q_over_box, vectorised over entries."""
     lx, hx, ly, hy = x0 - mx, x1 - mx, y0 - my, y1 - my
     in_x = (lx <= 0) & (hx >= 0)
     in_y = (ly <= 0) & (hy >= 0)

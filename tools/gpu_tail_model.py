@@ -39,7 +39,7 @@ def analyse(name, sc, W, H):
     bs = img[off_bs:off_bs + nt * 16].view(torch.int32).view(nt, 4).cpu().numpy().astype(np.int64)
     res = {"R": int(out["R"]), "tiles": nt, "fwd_steps": int(bs.sum())}
     np.save(os.path.join(ROOT, "gpurun_out", "block_steps_" + name.split()[-1] + ".npy"), bs.astype(np.int32))
-    # forward: workgroup b -> tile (b >> 5) * 8 + (b & 7), quad (b & 31) >> 3  (render_fwd.hip)
+    # forward: workgroup b -> tile (b >> 5) * 8 + (b & 7), quad (b & 31) >> 3  (csrc/gsr_blend.h block8_of_workgroup)
     groups = (nt + 7) // 8
     b = np.arange(groups * 32)
     tl, quad = (b >> 5) * 8 + (b & 7), (b & 31) >> 3

@@ -19,6 +19,7 @@ global access merged into one generic-pointer access: emit_scatter read its LDS 
 until the two sources got separate loops) and the lengths of all chains >= 3."""
 from __future__ import annotations
 
+import importlib.util
 import os
 import re
 import subprocess
@@ -27,11 +28,17 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gaussian-splatting_amd", "csrc")
-UNITS = {"preprocess.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"], "sort.hip": [], "depthsort.hip": [], "binning.hip": [],
-         "tilesort.hip": [], "route.hip": [], "render_fwd.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"], "render_bwd.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"],
-         "contrib.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"],
-         "adam.hip": ["-ffp-contract=off"], "ssim.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"], "knn.hip": ["-ffp-contract=off"],
-         "density.hip": ["-ffp-contract=off"]}
+
+
+def _build_units():
+    """The per-unit compiler flags of gaussian-splatting_amd/build.py (its UNITS table, loaded by path: the one place they are written down)."""
+    spec = importlib.util.spec_from_file_location("gsr_build_units", os.path.join(ROOT, "gaussian-splatting_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return {src: list(flags) for src, flags in mod.UNITS if src.endswith(".hip")}
+
+
+UNITS = _build_units()
 
 
 def demangle_short(name: str) -> str:
