@@ -681,7 +681,7 @@ mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __res
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = means3D[i * 3 + 0], y = means3D[i * 3 + 1], z = means3D[i * 3 + 2];
         const float pvz = vm[2] * x + vm[6] * y + vm[10] * z + vm[14];
-        present[i] = pvz > GSR_NEAR_Z ? 1 : 0;
+        present[i] = (pvz > GSR_NEAR_Z && pvz < INFINITY) ? 1 : 0;      // (a mean at +inf is culled by the projection -- its rectangle is empty --: not visible here either)
     }
 }
 

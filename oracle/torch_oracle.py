@@ -132,9 +132,27 @@ class _ConicFromCov(torch.autograd.Function):
         return ga, gb, gc
 
 
+class _StMin(torch.autograd.Function):
+    """IEEE fminf(cap, x) in the forward -- NaN gives cap (fminf returns its non-NaN operand), +inf gives cap, -inf stays -inf --
+    and the identity in the backward (reference's alpha cap convention).  csrc/gsr_blend.h alpha_of."""
+
+    @staticmethod
+    def forward(ctx, x, cap):
+        return torch.where(x <= cap, x, torch.full_like(x, cap))
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
 def _st_min(x, cap):
-    """min(cap, x) in the forward, identity in the backward (reference's alpha cap convention)."""
-    return x + (torch.clamp(x, max=cap) - x).detach()
+    """min(cap, x) in the forward under IEEE fminf rules, identity in the backward."""
+    return _StMin.apply(x, cap)
+
+
+def _fmax0(x):
+    """IEEE fmaxf(x, 0): NaN and -inf give 0, +inf stays; the gradient passes where x >= 0 (torch.clamp_min's rule for finite x)."""
+    return torch.where(x >= 0, x, torch.zeros_like(x))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -201,7 +219,7 @@ def eval_sh_colors(deg, shs, means3D, campos, dtype):
                           + c(SH_C3[6]) * x * (xx - c(3.0) * yy) * sh[:, 15])
     result = result + c(0.5)
     clamped = (result < 0).detach()
-    return torch.clamp_min(result, 0.0), clamped
+    return _fmax0(result), clamped
 
 
 def preprocess(means3D, opacities, s: Settings, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -459,8 +477,10 @@ def _blend_tile(px, py, xy, conic, opac, rgb, invd, want_fragile=False, frag_eps
         pos = torch.arange(1, N + 1, dtype=torch.int64)[None, :]
         n_contrib = (contrib.to(torch.int64) * pos).max(dim=1).values
     w = torch.where(contrib, alpha_eff * Texcl, torch.zeros_like(alpha_eff))
-    C = (w[:, :, None] * rgb[None, :, :]).sum(dim=1)
-    D = (w * invd[None, :]).sum(dim=1)
+    # (nothing of an entry that does not contribute reaches the sums -- a sequential blend never evaluates 0 * rgb of a skipped entry,
+    #  which would turn a NaN / inf colour into NaN at every pixel of the tile)
+    C = torch.where(contrib[:, :, None], w[:, :, None] * rgb[None, :, :], torch.zeros((), dtype=dtype)).sum(dim=1)
+    D = torch.where(contrib, w * invd[None, :], torch.zeros((), dtype=dtype)).sum(dim=1)
     T_at = torch.gather(Texcl, 1, first_dead[:, None])[:, 0]
     final_T = torch.where(any_dead, T_at, Tincl[:, -1])
     fragile = torch.zeros(n, dtype=torch.bool)
@@ -550,8 +570,8 @@ def rasterize(means3D, means2D, opacities, s: Settings, shs=None, colors_precomp
 
 
 def mark_visible(means3D, viewmatrix):
-    """checkFrustum / markVisible: in front of the 0.2 near plane."""
+    """checkFrustum / markVisible: in front of the 0.2 near plane, at a finite depth (a mean at +inf projects nowhere)."""
     vm = viewmatrix.detach().to("cpu", means3D.dtype).reshape(16)
     x, y, z = _cols(means3D)
     pvz = vm[2] * x + vm[6] * y + vm[10] * z + vm[14]
-    return pvz > NEAR_Z
+    return (pvz > NEAR_Z) & (pvz < math.inf)

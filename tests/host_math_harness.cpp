@@ -14,6 +14,9 @@ struct HostCam {
     float view[16], proj[16], campos[3];
 };
 
+static int g_snug = 1;      // 1 = the product's snug tile rectangle (the default), 0 = the reference's tile square (the library's snug_tiles option)
+void host_set_snug(int on) { g_snug = on ? 1 : 0; }
+
 static GsrCam to_cam(const HostCam* h) {
     GsrCam c;
     c.W = h->W; c.H = h->H;
@@ -22,7 +25,7 @@ static GsrCam to_cam(const HostCam* h) {
     c.focal_y = (float)h->H / (2.0f * h->tanfovy);
     c.limx = 1.3f * h->tanfovx; c.limy = 1.3f * h->tanfovy;
     c.scale_modifier = h->scale_modifier;
-    c.sh_degree = h->sh_degree; c.M = h->M; c.antialiasing = h->antialiasing; c.snug = 1;
+    c.sh_degree = h->sh_degree; c.M = h->M; c.antialiasing = h->antialiasing; c.snug = g_snug;
     c.tile_y0 = h->tile_y0; c.tile_y1 = h->tile_y1 <= 0 ? c.gy : h->tile_y1;
     memcpy(c.view, h->view, sizeof(c.view)); memcpy(c.proj, h->proj, sizeof(c.proj));
     memcpy(c.campos, h->campos, sizeof(c.campos));

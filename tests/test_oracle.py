@@ -195,6 +195,51 @@ def test_tie_order_follows_gaussian_index():
             assert pl[a:b].tolist() == sorted(pl[a:b].tolist())
 
 
+# ----------------------------------------------------------------------------- non-finite opacity and colour: IEEE fminf / fmaxf, a sequential blend
+def _blend64(px, centres_x, opac, rgb):
+    """O._blend_tile in fp64 for pixels (px, 0) and entries centred at (centres_x, 0) with the unit conic: power = -0.5 dx^2."""
+    f = lambda v: torch.tensor(v, dtype=torch.float64)      # noqa: E731
+    n = len(centres_x)
+    xy = torch.stack([f(centres_x), torch.zeros(n, dtype=torch.float64)], dim=1)
+    conic = f([[1.0, 0.0, 1.0]] * n)
+    return O._blend_tile(f(px), torch.zeros(len(px), dtype=torch.float64), xy, conic, f(opac), f(rgb), f([1.0, 0.5, 0.25][:n]))
+
+
+def test_kat_nan_opacity_blends_with_alpha_099():
+    """alpha = fminf(0.99, opacity G) returns its non-NaN operand: the NaN entry takes 0.99 of what the first one left.
+    w = 0.5, 0.99 * 0.5 = 0.495, 0.5 * (0.5 * 0.01) = 0.0025; T = 0.0025; inverse depth = 0.5 * 1 + 0.495 * 0.5 + 0.0025 * 0.25."""
+    C, D, fT, nc, _ = _blend64([0.0], [0.0, 0.0, 0.0], [0.5, math.nan, 0.5], [[1.0, 0, 0], [0, 1.0, 0], [0, 0, 1.0]])
+    assert torch.allclose(C[0], torch.tensor([0.5, 0.495, 0.0025], dtype=torch.float64), rtol=0, atol=1e-15)
+    assert abs(float(fT[0]) - 0.0025) < 1e-15 and int(nc[0]) == 3 and abs(float(D[0]) - 0.748125) < 1e-15
+
+
+def test_kat_inf_opacity_blends_with_alpha_099_also_where_g_underflows():
+    """+inf * G is +inf -> 0.99 at the centre; 40 pixels away G = exp(-800) underflows to 0 (fp64 too), inf * 0 is NaN -> 0.99 as well:
+    pixel 0: w = 0.99, 0.5 * 0.01 = 0.005; pixel 40: the finite entry is out of reach (alpha = 0 < 1/255), the infinite one gives 0.99."""
+    C, D, fT, nc, _ = _blend64([0.0, 40.0], [0.0, 0.0], [math.inf, 0.5], [[1.0, 0, 0], [0, 1.0, 0]])
+    assert torch.allclose(C, torch.tensor([[0.99, 0.005, 0.0], [0.99, 0.0, 0.0]], dtype=torch.float64), rtol=0, atol=1e-15)
+    assert torch.allclose(fT, torch.tensor([0.005, 0.01], dtype=torch.float64), rtol=0, atol=1e-15) and nc.tolist() == [2, 1]
+
+
+def test_kat_nan_and_minus_inf_colour_display_as_zero():
+    """The colour clamp is fmaxf(x + 0.5, 0): NaN and -inf give 0 (the flag `clamped` stays x < 0: false for NaN), +inf stays.  Degree 0:
+    rgb = SH_C0 * dc + 0.5; blended at opacity 0.5 the pixel is 0.5 * rgb, finite."""
+    dc = torch.tensor([[[math.nan, -math.inf, 1.0]], [[math.inf, -3.0, 0.0]]], dtype=torch.float64)
+    rgb, clamped = O.eval_sh_colors(0, dc, torch.tensor([[0.0, 0.0, 4.0]] * 2, dtype=torch.float64), torch.zeros(3, dtype=torch.float64), torch.float64)
+    assert rgb[0].tolist() == [0.0, 0.0, O.SH_C0 + 0.5] and rgb[1].tolist() == [math.inf, 0.0, 0.5]
+    assert clamped.tolist() == [[False, True, False], [False, True, False]]
+    C = _blend64([0.0], [0.0], [0.5], [rgb[0].tolist()])[0]
+    assert C[0].tolist() == [0.0, 0.0, 0.5 * (O.SH_C0 + 0.5)]
+
+
+def test_kat_inf_colour_stays_inside_the_pixels_where_its_entry_contributes():
+    """Entry 0 (infinite red) reaches pixel 0 only; at pixel 40 its alpha is 0 and a sequential blend skips it -- no 0 * inf there:
+    pixel 0 = 0.5 * (inf, 0.5, 0.25), pixel 40 = 0.5 * (0.2, 0.4, 0.6) of entry 1."""
+    C, D, fT, nc, _ = _blend64([0.0, 40.0], [0.0, 40.0], [0.5, 0.5], [[math.inf, 0.5, 0.25], [0.2, 0.4, 0.6]])
+    assert C[0].tolist() == [math.inf, 0.25, 0.125] and C[1].tolist() == [0.1, 0.2, 0.3]
+    assert D.tolist() == [0.5, 0.25] and fT.tolist() == [0.5, 0.5] and nc.tolist() == [1, 2]
+
+
 # ----------------------------------------------------------------------------- snug tile rectangles
 @pytest.mark.parametrize("maker,aa,size", [(lambda c: make_scene(3000, c, seed=2, s_med=0.03), False, (250, 131)),
                                            (lambda c: make_edge_scene(3000, c, seed=8), True, (250, 131)),

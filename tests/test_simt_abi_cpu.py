@@ -52,17 +52,38 @@ def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+GUARD, GUARD_BYTE = 64, 0xA5      # every buffer handed to the library ends in 64 bytes of a fixed pattern it must leave alone (guards_intact)
+
+
+def guarded(shape, dtype):
+    """A zeroed array of `shape` whose storage goes on for GUARD bytes of GUARD_BYTE -> (array, storage)."""
+    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    raw = np.full(n + GUARD, GUARD_BYTE, dtype=np.uint8)
+    raw[:n] = 0
+    return raw[:n].view(dtype).reshape(shape), raw
+
+
+def guards_intact(named_storage):
+    """[(name, storage)]: the GUARD bytes behind every array are as they were written -- nothing ran past its end."""
+    for name, raw in named_storage:
+        assert raw.size >= GUARD and bool((raw[-GUARD:] == GUARD_BYTE).all()), f"{name}: the bytes behind the buffer were overwritten"
+
+
 class Buffer:
-    """A caller-owned scratch buffer behind a resize callback (diff_gaussian_rasterization._Buffer with numpy instead of device memory)."""
+    """A caller-owned scratch buffer behind a resize callback (diff_gaussian_rasterization._Buffer with numpy instead of device memory): the bytes
+    asked for and GUARD guard bytes behind them."""
 
     def __init__(self):
-        self.a = np.zeros(16, dtype=np.uint8)
+        self.a = np.full(16 + GUARD, GUARD_BYTE, dtype=np.uint8)
+        self.n = 16
         self.calls = 0
 
         def resize(_user, nbytes):
             self.calls += 1
-            if self.a.size < nbytes:
-                self.a = np.zeros(nbytes + 64, dtype=np.uint8)
+            if self.n < nbytes:
+                self.a = np.full(nbytes + GUARD, GUARD_BYTE, dtype=np.uint8)
+                self.a[:nbytes] = 0
+                self.n = nbytes
             return self.a.ctypes.data
         self.cb = RESIZE(resize)
 
@@ -88,7 +109,7 @@ def forward(lib, s, sc, colors=None, cov=None, tile_rows=None, no_backward=False
     arr = dict(means3D=f32(sc.means3D), shs=None if colors is not None else f32(sc.shs), colors=f32(colors), opacities=f32(sc.opacities),
                scales=None if cov is not None else f32(sc.scales), rotations=None if cov is not None else f32(sc.rotations), cov=f32(cov))
     M = 0 if colors is not None else sc.shs.shape[1]
-    color, invd, radii = np.zeros((3, H, W), np.float32), np.zeros((1, H, W), np.float32), np.zeros(max(P, 1), np.int32)
+    (color, color_s), (invd, invd_s), (radii, radii_s) = guarded((3, H, W), np.float32), guarded((1, H, W), np.float32), guarded(max(P, 1), np.int32)
     geom, binning, img = Buffer(), Buffer(), Buffer()
     nr = C.c_int32(0)
     rc = lib.gsr_rasterize_forward(C.byref(rs), P, M, ptr(arr["means3D"]), ptr(arr["shs"]), ptr(arr["colors"]), ptr(arr["opacities"]), ptr(arr["scales"]),
@@ -99,7 +120,9 @@ def forward(lib, s, sc, colors=None, cov=None, tile_rows=None, no_backward=False
     assert rc == 0, lib.gsr_last_error()
     R = int(nr.value)
     out = {"rc": 0, "color": torch.from_numpy(color), "invdepth": torch.from_numpy(invd), "radii": torch.from_numpy(radii[:P]), "R": R,
-           "state": (rs, keep, arr, M, geom, binning, img, radii)}
+           "state": (rs, keep, arr, M, geom, binning, img, radii),
+           "guards": [("color", color_s), ("invdepth", invd_s), ("radii", radii_s), ("geom", geom.a), ("binning", binning.a), ("image state", img.a)]}
+    guards_intact(out["guards"])
     if P == 0:
         return out
     v = Views()
@@ -117,9 +140,13 @@ def forward(lib, s, sc, colors=None, cov=None, tile_rows=None, no_backward=False
 def backward(lib, s, sc, out, dL_dcolor, dL_dinvdepth=None):
     rs, keep, arr, M, geom, binning, img, radii = out["state"]
     P, R = sc.P, out["R"]
-    g = dict(means2D=np.zeros((P, 3), np.float32), colors=np.zeros((P, 3), np.float32), opacities=np.zeros((P, 1), np.float32), means3D=np.zeros((P, 3), np.float32),
-             cov=np.zeros((P, 6), np.float32), shs=np.zeros((P, max(M, 1), 3), np.float32), scales=np.zeros((P, 3), np.float32), rotations=np.zeros((P, 4), np.float32))
-    scratch = np.zeros(lib.gsr_backward_scratch_bytes(P, R) + 64, dtype=np.uint8)
+    shapes = dict(means2D=(P, 3), colors=(P, 3), opacities=(P, 1), means3D=(P, 3), cov=(P, 6), shs=(P, max(M, 1), 3), scales=(P, 3), rotations=(P, 4))
+    g, storage = {}, []
+    for k, shape in shapes.items():
+        g[k], raw = guarded(shape, np.float32)
+        storage.append((f"dL/d{k}", raw))
+    scratch, raw = guarded(lib.gsr_backward_scratch_bytes(P, R), np.uint8)
+    storage.append(("backward scratch", raw))
     dcol, dinv = f32(dL_dcolor), f32(dL_dinvdepth)
     rc = lib.gsr_rasterize_backward(C.byref(rs), P, M, R, ptr(arr["means3D"]), ptr(arr["shs"]), ptr(arr["colors"]), ptr(arr["opacities"]), ptr(arr["scales"]),
                                     ptr(arr["rotations"]), ptr(arr["cov"]), ptr(radii), ptr(geom.a), ptr(binning.a), ptr(img.a), ptr(dcol), ptr(dinv),
@@ -128,6 +155,7 @@ def backward(lib, s, sc, out, dL_dcolor, dL_dinvdepth=None):
                                     ptr(g["scales"]) if arr["scales"] is not None else None, ptr(g["rotations"]) if arr["rotations"] is not None else None,
                                     ptr(scratch), None, None)
     assert rc == 0, lib.gsr_last_error()
+    guards_intact(storage + out["guards"])
     return g
 
 
