@@ -1165,6 +1165,34 @@ int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num
     return GSR_OK;
 }
 
+int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                    const void* image_buffer, const GsrPixelProbeOut* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GsrCamDev cam;
+    int rc = make_cam(settings, 0, cam);
+    if (rc != GSR_OK) return rc;
+    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
+    if (!out) return fail(GSR_ERR_INVALID_ARG, "out (GsrPixelProbeOut) is NULL");
+    if (!(out->threshold > 0.0f && out->threshold < 1.0f))      // (a NaN fails both comparisons)
+        return fail(GSR_ERR_INVALID_ARG, "GsrPixelProbeOut.threshold must be inside (0, 1)");
+    const int64_t R = num_rendered;
+    if (P > 0 && R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
+    if (P == 0 || R == 0) {      // no state to read: the defaults over the band
+        gsr_launch_pixel_probe_defaults(cam, *out, st);
+        HIP_OK(hipGetLastError());
+        return GSR_OK;
+    }
+    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
+    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
+    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
+    const int list_buf = list_buffer_index(cam.gx * cam.gy);
+    gsr_launch_pixel_probe(cam, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, *out, st);
+    STAGE_CHECK("pixel probe");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 // gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera
 static int backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
                                const float* colors_precomp, const float* opacities, const float* scales,

@@ -1,6 +1,6 @@
-// What the three kernels that walk the per-tile splat lists must compute IDENTICALLY (device only): the forward blend (render_fwd.hip) decides which
-// entries a wave keeps and which pixels take them; the blend backward (render_bwd.hip) and the contribution statistics (contrib.hip) trust its
-// n_contrib and re-derive alpha and the hard masks, which is correct only while those are the forward's bits.  One definition each of the box
+// What the kernels that walk the per-tile splat lists must compute IDENTICALLY (device only): the forward blend (render_fwd.hip) decides which
+// entries a wave keeps and which pixels take them; the blend backward (render_bwd.hip), the contribution statistics (contrib.hip) and the per-pixel
+// probe (probe.hip) trust its n_contrib and re-derive alpha and the hard masks, which is correct only while those are the forward's bits.  One definition each of the box
 // test, the conic pre-scale, the exponent / alpha sequence, the emission index and the placement of a wave per 8x8 pixel block.  The loops, the
 // prefetch pipeline, the LDS parking and the per-kernel step bodies stay in their files.  Every helper here compiles to the instructions of the
 // code it replaced, kernel by kernel; one that does not is not shared (see Block8).

@@ -337,6 +337,12 @@ void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const
                                    const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count /*each [P] or NULL*/,
                                    int accumulate, hipStream_t st);
 
+// probe.hip: per-pixel probe (gsr_pixel_probe).  No scratch.  The kernel writes every in-band, in-image pixel of the non-NULL arrays, the defaults
+// included; _defaults fills the band's rows without reading any state (the call with P == 0 or num_rendered == 0).
+void gsr_launch_pixel_probe(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
+                            const GsrPixelProbeOut& out, hipStream_t st);
+void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOut& out, hipStream_t st);
+
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                      int step, hipStream_t st);

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import GsrError, GsrRasterSettings, RESIZE_FN  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam", "rasterize_gaussians", "GsrError",
-           "ContributionStats", "contribution_stats"]
+           "ContributionStats", "contribution_stats", "PixelProbe", "pixel_probe"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -361,6 +361,34 @@ def _rasterizer_nodes(t: torch.Tensor) -> list:
     return found
 
 
+class _SavedState(NamedTuple):
+    """What a read-only entry point needs of the one rasterizer call behind a tensor (_saved_state)."""
+    settings: GaussianRasterizationSettings
+    tile_rows: Optional[Tuple[int, int]]
+    P: int
+    fwd: _Forward
+    device: torch.device
+
+
+def _saved_state(rendered, who: str, standalone: str) -> _SavedState:
+    """The state that the ONE _RasterizeGaussians node behind `rendered` keeps for its backward; GsrError for no node, several nodes, a node of the
+    multi-GPU renderers or freed state.  `who` / `standalone` name the caller and its no_grad counterpart in the messages."""
+    nodes = _rasterizer_nodes(rendered) if isinstance(rendered, torch.Tensor) else []
+    if len(nodes) != 1:
+        raise GsrError(("no rasterizer call found behind `rendered`: it must be computed from a GaussianRasterizer output with gradients enabled "
+                        f"(under torch.no_grad() use GaussianRasterizer.{standalone})") if not nodes else
+                       f"`rendered` depends on {len(nodes)} rasterizer calls: pass a tensor computed from exactly one")
+    ctx = nodes[0]
+    if ctx.grad_sync is not None:
+        raise GsrError(f"{who} does not support the multi-GPU renderers (a rasterizer call with grad_sync)")
+    try:
+        saved = ctx.saved_tensors
+    except RuntimeError as e:
+        raise GsrError(f"the rasterizer call's state has been freed: call {who} before backward(), or use retain_graph=True") from e
+    means3D, geom, binning, img = saved[0], saved[8], saved[9], saved[10]
+    return _SavedState(ctx.raster_settings, ctx.tile_rows, int(means3D.shape[0]), _Forward(geom, binning, img, ctx.num_rendered), means3D.device)
+
+
 def contribution_stats(rendered: torch.Tensor, pixel_weight: Optional[torch.Tensor] = None,
                        into: Optional[ContributionStats] = None) -> ContributionStats:
     """What every Gaussian gave to a frame that has ALREADY been rendered (no reference counterpart): `rendered` is any tensor computed
@@ -370,26 +398,56 @@ def contribution_stats(rendered: torch.Tensor, pixel_weight: Optional[torch.Tens
     a mask: pixels with weight 0 are excluded); None is 1 everywhere.  `into` (a ContributionStats of an earlier call) is combined in
     place -- sum + frame, max(max, frame), count + frame -- and returned, so scores over many views build up without torch ops.
     With `tile_rows` the statistics are the band's.  Nothing here is differentiable; two calls give the same bits."""
-    nodes = _rasterizer_nodes(rendered) if isinstance(rendered, torch.Tensor) else []
-    if len(nodes) != 1:
-        raise GsrError(("no rasterizer call found behind `rendered`: it must be computed from a GaussianRasterizer output with gradients enabled "
-                        "(under torch.no_grad() use GaussianRasterizer.contributions)") if not nodes else
-                       f"`rendered` depends on {len(nodes)} rasterizer calls: pass a tensor computed from exactly one")
-    ctx = nodes[0]
-    if ctx.grad_sync is not None:
-        raise GsrError("contribution_stats does not support the multi-GPU renderers (a rasterizer call with grad_sync)")
-    try:
-        saved = ctx.saved_tensors
-    except RuntimeError as e:
-        raise GsrError("the rasterizer call's state has been freed: call contribution_stats before backward(), or use retain_graph=True") from e
-    means3D, geom, binning, img = saved[0], saved[8], saved[9], saved[10]
-    device, P = means3D.device, int(means3D.shape[0])
-    rs = ctx.raster_settings
-    pw = _pixel_weight(pixel_weight, int(rs.image_height), int(rs.image_width), device)
+    st = _saved_state(rendered, "contribution_stats", "contributions")
+    rs = st.settings
+    pw = _pixel_weight(pixel_weight, int(rs.image_height), int(rs.image_width), st.device)
     keep: list = []
-    with torch.no_grad(), torch.cuda.device(device):
-        s = _make_settings(rs, keep, ctx.tile_rows, bg_image=True)
-        return _contribution_stats(s, P, _Forward(geom, binning, img, ctx.num_rendered), pw, into, device)
+    with torch.no_grad(), torch.cuda.device(st.device):
+        s = _make_settings(rs, keep, st.tile_rows, bg_image=True)
+        return _contribution_stats(s, st.P, st.fwd, pw, into, st.device)
+
+
+class PixelProbe(NamedTuple):
+    """Per-pixel probe of one forward (include/gsr.h gsr_pixel_probe), every field [H,W]: with w = alpha * T the blend weight of a contributor at
+    view-space depth z, front to back: expected_depth = sum w z (float32, not normalised: divide by alpha), median_depth / median_id = z and Gaussian
+    index of the first contributor behind which transmittance is < threshold (0.0 / -1: none), top_id / top_weight = index and w of the contributor
+    with the largest w (-1 / 0.0: none; the nearest wins ties), count = contributors (ids and count int32)."""
+    expected_depth: torch.Tensor
+    median_depth: torch.Tensor
+    median_id: torch.Tensor
+    top_id: torch.Tensor
+    top_weight: torch.Tensor
+    count: torch.Tensor
+
+
+def _pixel_probe(s, P, fwd: _Forward, threshold: float, H: int, W: int, device) -> PixelProbe:
+    """gsr_pixel_probe on the state a tracking forward left.  The arrays are allocated with the defaults: with `tile_rows` the library leaves
+    pixels outside the band untouched."""
+    lib = _lib.load()
+    threshold = float(threshold)
+    if not 0.0 < threshold < 1.0:
+        raise GsrError(f"threshold must be inside (0, 1), got {threshold}")
+    f = lambda: torch.zeros(H, W, dtype=torch.float32, device=device)                        # noqa: E731
+    i = lambda v: torch.full((H, W), v, dtype=torch.int32, device=device)                   # noqa: E731
+    out = PixelProbe(f(), f(), i(-1), i(-1), f(), i(0))
+    rec = _lib.PixelProbeOut(*[t.data_ptr() for t in out], threshold, 0)
+    _lib.check(lib.gsr_pixel_probe(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), C.byref(rec),
+                                   _stream_ptr(device)), "gsr_pixel_probe")
+    return out
+
+
+def pixel_probe(rendered: torch.Tensor, threshold: float = 0.5) -> PixelProbe:
+    """What a frame that has ALREADY been rendered means for every pixel (no reference counterpart): median / expected depth, the Gaussian under the
+    pixel, the number of blended Gaussians -- a PixelProbe.  `rendered` and the state it is read from are `contribution_stats`'s: any tensor computed
+    from one rasterizer call's outputs with gradients enabled, before `backward()` frees the state (or with `retain_graph=True`); no second forward.
+    `threshold` in (0, 1) is the transmittance that defines median_depth / median_id (0.5: the median).  With `tile_rows`, pixels outside the band
+    hold the defaults (0, -1).  Nothing here is differentiable; two calls give the same bits."""
+    st = _saved_state(rendered, "pixel_probe", "probe")
+    rs = st.settings
+    keep: list = []
+    with torch.no_grad(), torch.cuda.device(st.device):
+        s = _make_settings(rs, keep, st.tile_rows, bg_image=True)
+        return _pixel_probe(s, st.P, st.fwd, threshold, int(rs.image_height), int(rs.image_width), st.device)
 
 
 def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
@@ -719,31 +777,48 @@ class GaussianRasterizer(nn.Module):
                                    self.raster_settings, getattr(self, "tile_rows", None), None, dc, self.return_alpha)
 
 
+    def _tracking_forward(self, means3D, opacities, scales, rotations, cov3D_precomp):
+        """-> (settings, P, _Forward, radii, keep): a tracking forward with zero colours (call it under no_grad and the device guard); honours
+        `tile_rows`.  `keep` holds what the settings point to."""
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        rs = self.raster_settings
+        device, P = means3D.device, int(means3D.shape[0])
+        H, W = int(rs.image_height), int(rs.image_width)
+        keep: list = []
+        s = _make_settings(rs, keep, getattr(self, "tile_rows", None), no_backward=False, bg_image=True)
+        inputs = (_f32c(means3D.detach()), None, torch.zeros(P, 3, dtype=torch.float32, device=device), _f32c(opacities.detach()),
+                  _f32c(scales.detach()) if scales is not None else None, _f32c(rotations.detach()) if rotations is not None else None,
+                  _f32c(cov3D_precomp.detach()) if cov3D_precomp is not None else None)
+        color = torch.empty(3, H, W, dtype=torch.float32, device=device)
+        invdepth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        radii = torch.empty(P, dtype=torch.int32, device=device)
+        return s, P, _rasterize_forward(s, P, 0, inputs, color, invdepth, radii, device), radii, keep
+
     def contributions(self, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, pixel_weight=None,
                       into: Optional[ContributionStats] = None):
         """-> (ContributionStats, radii[P]): the statistics of `contribution_stats` for this camera without a render of one's own to hand
         (no reference counterpart): runs a tracking forward with zero colours under no_grad, honours `tile_rows`, keeps nothing."""
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         _lib.load()
         _require_cuda(means3D, "means3D")
         rs = self.raster_settings
-        device, P = means3D.device, int(means3D.shape[0])
-        H, W = int(rs.image_height), int(rs.image_width)
-        pw = _pixel_weight(pixel_weight, H, W, device)
-        keep: list = []
+        device = means3D.device
+        pw = _pixel_weight(pixel_weight, int(rs.image_height), int(rs.image_width), device)
         with torch.no_grad(), torch.cuda.device(device):
-            tile_rows = getattr(self, "tile_rows", None)
-            s = _make_settings(rs, keep, tile_rows, no_backward=False, bg_image=True)
-            inputs = (_f32c(means3D.detach()), None, torch.zeros(P, 3, dtype=torch.float32, device=device), _f32c(opacities.detach()),
-                      _f32c(scales.detach()) if scales is not None else None, _f32c(rotations.detach()) if rotations is not None else None,
-                      _f32c(cov3D_precomp.detach()) if cov3D_precomp is not None else None)
-            color = torch.empty(3, H, W, dtype=torch.float32, device=device)
-            invdepth = torch.empty(1, H, W, dtype=torch.float32, device=device)
-            radii = torch.empty(P, dtype=torch.int32, device=device)
-            fwd = _rasterize_forward(s, P, 0, inputs, color, invdepth, radii, device)
+            s, P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
             return _contribution_stats(s, P, fwd, pw, into, device), radii
+
+    def probe(self, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, threshold: float = 0.5):
+        """-> (PixelProbe, radii[P]): the per-pixel probe of `pixel_probe` for this camera without a render of one's own to hand (no reference
+        counterpart): runs a tracking forward with zero colours under no_grad, honours `tile_rows`, keeps nothing."""
+        _lib.load()
+        _require_cuda(means3D, "means3D")
+        rs = self.raster_settings
+        device = means3D.device
+        with torch.no_grad(), torch.cuda.device(device):
+            s, P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
+            return _pixel_probe(s, P, fwd, threshold, int(rs.image_height), int(rs.image_width), device), radii
 
 
 class SparseGaussianAdam(torch.optim.Adam):

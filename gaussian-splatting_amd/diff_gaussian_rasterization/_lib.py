@@ -82,6 +82,12 @@ class ContribOut(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class PixelProbeOut(C.Structure):
+    """GsrPixelProbeOut of include/gsr.h (gsr_pixel_probe)."""
+    _fields_ = [("expected_depth", C.c_void_p), ("median_depth", C.c_void_p), ("median_id", C.c_void_p), ("top_id", C.c_void_p),
+                ("top_weight", C.c_void_p), ("count", C.c_void_p), ("threshold", C.c_float), ("reserved", C.c_int32)]
+
+
 class AdamTensor(C.Structure):
     """GsrAdamTensor of include/gsr.h (gsr_adam_step_multi)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
@@ -119,6 +125,7 @@ SIGNATURES = {
     "gsr_backward_blend_composite": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), C.POINTER(CompositeGrads), _vp]),
     "gsr_contribution_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "gsr_contribution_stats": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.POINTER(ContribOut), _vp]),
+    "gsr_pixel_probe": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 3 + [C.POINTER(PixelProbeOut), _vp]),
     "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
     "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
     "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

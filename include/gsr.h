@@ -290,6 +290,44 @@ int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num
                            const GsrContribOut* out, void* stream);
 
 /*
+ * Per-pixel probe (no reference counterpart): what one forward meant for every PIXEL beyond colour, inverse depth and alpha -- depth
+ * maps that can be fused, the Gaussian under a pixel, the number of blended Gaussians -- read from the state of
+ * gsr_contribution_stats: gsr_rasterize_forward / gsr_rasterize_forward_composite run with no_backward == 0, the same settings, the
+ * same buffers, num_rendered as returned.  The states of the record entry points (from_splats / from_packed / from_segments) are not
+ * supported.  Nothing is differentiable.
+ * Conventions, those of gsr_contribution_stats: Gaussian g contributes to pixel p exactly when the forward blended it there -- its entry
+ * is valid (power <= 0 and alpha >= 1/255, alpha capped at 0.99) and its list position is <= n_contrib[p]; n_contrib is the authority
+ * on termination (T < 1e-4 is not re-tested).  Front to back, T is the product of (1 - alpha) over the contributors in front of an
+ * entry, w = alpha * T its blend weight, T' = T (1 - alpha) the transmittance behind it, z its view-space depth (the preprocess's
+ * depth, the 1/z of out_invdepth) and g the caller's Gaussian index.  Per pixel of the rendered band:
+ *   expected_depth            = sum over contributors of w z, summed in fp32 in list order.  NOT normalised: divide by alpha
+ *                               (1 - T_final) for the normalised form.  Complements out_invdepth = sum w / z.
+ *   median_depth, median_id   = z and g of the FIRST contributor with T' < threshold (0.5: the median depth, where transmittance
+ *                               crosses 1/2); 0.0f and -1 if the pixel has none.
+ *   top_id, top_weight        = g and w of the contributor with the largest w; a later one replaces an earlier one on strict >
+ *                               only, so the nearest wins exact ties; -1 and 0.0f without a contributor.
+ *   count                     = number of contributors (n_contrib is a list position, not a count).
+ * Every pixel of the band inside the image is written, pixels without a contributor with the defaults above (0.0f, 0.0f, -1, -1,
+ * 0.0f, 0); with a band of tile rows (tile_y0 / tile_y1) pixels outside the band are not touched.  P == 0 or num_rendered == 0: the
+ * defaults are written over the band and the state buffers are not read (they may be NULL).  Bit-reproducible: one lane per pixel,
+ * fixed order, no atomics.  No scratch.  Each output pointer may be NULL.  A NULL `out`, a threshold outside (0,1) or NaN, negative
+ * P / num_rendered, or NULL state buffers with P > 0 and num_rendered > 0 are GSR_ERR_INVALID_ARG.
+ */
+typedef struct GsrPixelProbeOut {
+    float*   expected_depth;  /* [H,W] or NULL */
+    float*   median_depth;    /* [H,W] or NULL */
+    int32_t* median_id;       /* [H,W] or NULL */
+    int32_t* top_id;          /* [H,W] or NULL */
+    float*   top_weight;      /* [H,W] or NULL */
+    int32_t* count;           /* [H,W] or NULL */
+    float    threshold;       /* transmittance threshold of the median, 0 < t < 1 (0.5: the median) */
+    int32_t  reserved;
+} GsrPixelProbeOut;
+int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                    const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                    const GsrPixelProbeOut* out, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
