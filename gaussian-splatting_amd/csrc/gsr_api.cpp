@@ -1053,8 +1053,12 @@ size_t gsr_composite_grad_scratch_bytes(int width, int height) {
 static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
                           const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
                           const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out, const GsrCompositeGrads* extra,
-                          void* stream) {
+                          void* stream, bool absgrad = false) {
     hipStream_t st = (hipStream_t)stream;
+#ifdef GSR_AB_VARIANTS
+    if (absgrad) return fail(GSR_ERR_UNSUPPORTED, "gsr_backward_blend_abs is not part of the measurement build (-DGSR_AB_VARIANTS)");
+#endif
+    if (absgrad && g_render_bwd_variant != 0) return fail(GSR_ERR_UNSUPPORTED, "gsr_backward_blend_abs needs the default blend backward (render_bwd_variant 0)");
     GsrCamDev cam;
     int rc = make_cam(settings, 0, cam);
     if (rc != GSR_OK) return rc;
@@ -1095,6 +1099,10 @@ static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_
             if (num_rendered > 0)
                 gsr_launch_render_backward(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps, nullptr,
                                            dL_dout_color, dL_dout_invdepth, sg, nullptr, nullptr, num_rendered, 1, 0, nullptr, st);
+        } else if (absgrad) {
+            gsr_launch_render_backward_abs(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
+                                           g_bwd_heavy_first ? im.tile_order : nullptr, dL_dout_color, dL_dout_invdepth, w.inst_grads, w.inst_flag,
+                                           num_rendered, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st, compp);
         } else {
             // (the flag words of the instances are cleared by the launcher: in the plan kernel's launch, or with a fill)
             gsr_launch_render_backward_composite(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
@@ -1108,6 +1116,8 @@ static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_
         StageTimer t(GSR_STAGE_GATHER_BWD, st);
         gsr_launch_reduce_instances(P, num_rendered, g.vals[depth_order_buffer_index()], g.offsets, g.splats, w.inst_grads,
                                     w.inst_flag, sg, w.unit_first, w.unit_piece, st);
+        if (absgrad)
+            gsr_launch_absgrad_reduce(P, num_rendered, g.vals[depth_order_buffer_index()], g.offsets, w.inst_grads, w.inst_flag, sg, st);
     }
     STAGE_CHECK("render backward reduce");
     HIP_OK(hipGetLastError());
@@ -1128,6 +1138,29 @@ int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32
     if (!extra) return fail(GSR_ERR_INVALID_ARG, "extra (GsrCompositeGrads) is NULL");
     return backward_blend(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, dL_dout_color, dL_dout_invdepth, bwd_scratch,
                           splat_grads_out, extra, stream);
+}
+
+int gsr_backward_blend_abs(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                           const void* binning_buffer, const void* image_buffer, const float* dL_dout_color,
+                           const float* dL_dout_invdepth, void* bwd_scratch, float** splat_grads_out,
+                           const GsrCompositeGrads* extra, void* stream) {
+    return backward_blend(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, dL_dout_color, dL_dout_invdepth, bwd_scratch,
+                          splat_grads_out, extra, stream, true);
+}
+
+int gsr_absgrad_from_records(const GsrRasterSettings* settings, int P, const float* splat_grads, float* means2D_abs, void* stream) {
+    GsrCamDev cam;
+    int rc = make_cam(settings, 0, cam);
+    if (rc != GSR_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!splat_grads || !means2D_abs) return fail(GSR_ERR_INVALID_ARG, "splat_grads / means2D_abs are NULL");
+    if (((uintptr_t)splat_grads) & 7) return fail(GSR_ERR_INVALID_ARG, "splat_grads must be 8-byte aligned");
+    gsr_launch_absgrad_from_records(P, cam.W, cam.H, splat_grads, means2D_abs, st);
+    STAGE_CHECK("absgrad from records");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
 }
 
 size_t gsr_contribution_scratch_bytes(int P, int64_t R) { (void)P; return gsr_carve_contrib(nullptr, R).bytes; }

@@ -296,6 +296,18 @@ void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ran
                                           const uint32_t* block_steps, uint32_t* tile_order, const float* dL_dpix, const float* dL_dinvdepth,
                                           float* splat_grads, float* inst_grads, uint32_t* inst_flag, int64_t R, int variant, int order_mode,
                                           unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp);
+// the walk's ABS instantiations (gsr_backward_blend_abs): the same launch (plan kernel, flags, order) with words 10, 11 of every instance record
+// carrying the two absolute sums of absgrad.hip; default kernel only (no measurement-build variant)
+void gsr_launch_render_backward_abs(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                                    const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                                    const uint32_t* block_steps, uint32_t* tile_order, const float* dL_dpix, const float* dL_dinvdepth,
+                                    float* inst_grads, uint32_t* inst_flag, int64_t R, int order_mode,
+                                    unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp);
+// absgrad.hip: words 10, 11 of splat_grads[g] <- the sum of words 10, 11 of g's flagged instance records (after gsr_launch_reduce_instances, same
+// stream); means2D_abs[P,3] = (0.5 W word 10, 0.5 H word 11, 0)
+void gsr_launch_absgrad_reduce(int P, int64_t R, const uint32_t* order, const uint32_t* offsets, const float* inst_grads, const uint32_t* inst_flag,
+                               float* splat_grads, hipStream_t st);
+void gsr_launch_absgrad_from_records(int P, int W, int H, const float* splat_grads, float* means2D_abs, hipStream_t st);
 // background gradient (render_bwd.hip): dL_dbg_image[c][p] = T(p) * dL_dpix[c][p] and / or dL_dbg[c] = sum over p, with T = final_T inside the
 // band's pixel rows [row0, row1) (1 where final_T is NULL: no Gaussian at all) and 0 outside.  partials: gsr_bg_grad_blocks(W * H) * 3 doubles.
 #define GSR_BG_GRAD_PIXELS 2048      // pixels per workgroup (256 threads x 8)

@@ -52,6 +52,12 @@ __device__ __forceinline__ void dpp_stage(float& c, float& a, float& b) {
     a = dpp_add<CTRL, 0xf>(a); dpp_pin(a);
     b = dpp_add<CTRL, 0xf>(b); dpp_pin(b);
 }
+// the same with the fourth chain of the ABS instantiations in front
+template <int CTRL>
+__device__ __forceinline__ void dpp_stage4(float& d, float& c, float& a, float& b) {
+    d = dpp_add<CTRL, 0xf>(d); dpp_pin(d);
+    dpp_stage<CTRL>(c, a, b);
+}
 
 // one step of a segmented inclusive scan over the wave: lanes whose DPP source lane carries the same segment id add its values
 template <int CTRL, int ROW_MASK>
@@ -118,6 +124,13 @@ constexpr int REC_STRIDE = 3;      // float4 per staged entry (48 B: 12-word str
 // per-pixel select count drops from six (T, acc, last colour, last alpha, w, dL/dalpha) to two (alpha, G).
 // HAS_DEPTH = false (no gradient arrives for the inverse-depth image: train.py without depth supervision) drops the
 // 1/depth term of cD, the tenth gradient value and one cross-lane reduction.
+// ABS = true (gsr_backward_blend_abs, include/gsr.h: the absolute screen-space gradient of AbsGS) adds two sums per (half tile, entry):
+// sum over the pixels of |m (A dx + B dy)| and |m (C dy + B dx)|, m the step's own m -- the per-pixel terms whose SIGNED sums are the
+// moments mx, my folded with the conic afterwards.  The conic is recovered from a2 / b2 / c2 by their constants: A dx + B dy =
+// -(2 a2 dx + b2 dy) / log2(e), and the common factor 1 / log2(e) is applied once per Gaussian by absgrad_reduce (absgrad.hip), so the
+// instance records' words 10, 11 -- padding otherwise -- carry the sums in log2 units.  The two sums travel in a chain of their own (v3):
+// folding them into v2 would change the association order of the colour / inverse-depth sums, and words 0..9 are the ABS = false bits.
+// With ABS = false every line compiles as before.
 struct BwdPix2 {
     v2f T, acc;
 };
@@ -126,7 +139,7 @@ struct BwdPix2 {
 #ifndef GSR_BWD_OCC
 #define GSR_BWD_OCC
 #endif
-template <bool HAS_DEPTH>
+template <bool HAS_DEPTH, bool ABS>
 __global__ void __launch_bounds__(64) GSR_BWD_OCC
 render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                 const float4* __restrict__ splats, const float* __restrict__ final_T,
@@ -301,10 +314,24 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
                 const v2f gd2 = w * dLd;
                 v2 = fold32(g_b, gd2.x + gd2.y);
             }
-            dpp_stage<0x111>(v2, v0, v1);
-            dpp_stage<0x112>(v2, v0, v1);
-            dpp_stage<0x114>(v2, v0, v1);
-            dpp_stage<0x118>(v2, v0, v1);
+            float v3 = 0.0f;                                             // ABS: -> slots 10 (lane 31), 11 (lane 63)
+            if (ABS) {
+                const float a2x2 = a2 + a2, b2dy = b2 * dy, c2dy2 = (c2 + c2) * dy;
+                const v2f tx = {fmaf(a2x2, dx.x, b2dy), fmaf(a2x2, dx.y, b2dy)};      // -log2(e) (A dx + B dy)
+                const v2f ty = {fmaf(b2, dx.x, c2dy2), fmaf(b2, dx.y, c2dy2)};        // -log2(e) (C dy + B dx)
+                v3 = fold32(fabsf(m.x * tx.x) + fabsf(m.y * tx.y), fabsf(m.x * ty.x) + fabsf(m.y * ty.y));
+                dpp_stage4<0x111>(v3, v2, v0, v1);
+                dpp_stage4<0x112>(v3, v2, v0, v1);
+                dpp_stage4<0x114>(v3, v2, v0, v1);
+                dpp_stage4<0x118>(v3, v2, v0, v1);
+                v3 = dpp_add<0x142, 0xa>(v3);
+                dpp_pin(v3);
+            } else {
+                dpp_stage<0x111>(v2, v0, v1);
+                dpp_stage<0x112>(v2, v0, v1);
+                dpp_stage<0x114>(v2, v0, v1);
+                dpp_stage<0x118>(v2, v0, v1);
+            }
             v2 = dpp_add<0x142, 0xa>(v2);
             if (!HAS_DEPTH) v2 = dpp_add<0x143, 0xc>(v2);
             dpp_pin(v2);
@@ -317,6 +344,7 @@ render_bwd_half(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ range
                 } else if (lane == 63) {
                     *reinterpret_cast<float2*>(&s_grad[j * 12 + 8]) = make_float2(v2, 0.0f);
                 }
+                if (ABS && (lane & 16)) s_grad[j * 12 + 10 + (lane >> 5)] = v3;
             }
             touched |= 1ull << j;
         }
@@ -790,7 +818,7 @@ void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uin
                             const uint32_t* block_steps, uint32_t* tile_order,
                             const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
                             uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st,
-                            const GsrCompositeDev* comp_in) {
+                            const GsrCompositeDev* comp_in, bool absgrad = false) {
     const GsrCompositeDev comp = comp_in ? *comp_in : GsrCompositeDev{nullptr, nullptr, nullptr};
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0) return;
@@ -829,14 +857,11 @@ void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uin
         (void)hipMemsetAsync(inst_flag, 0, (size_t)R * 4, st);
     }
     const int wave_order = (tile_order && order_mode == 3) ? 1 : 0;
-    if (dL_dinvdepth)
-        hipLaunchKernelGGL(render_bwd_half<true>, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats,
-                           final_T, n_contrib, dL_dpix, dL_dinvdepth, reinterpret_cast<float4*>(inst_grads),
-                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters, comp);
-    else
-        hipLaunchKernelGGL(render_bwd_half<false>, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats,
-                           final_T, n_contrib, dL_dpix, dL_dinvdepth, reinterpret_cast<float4*>(inst_grads),
-                           reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters, comp);
+    auto walk = dL_dinvdepth ? (absgrad ? render_bwd_half<true, true> : render_bwd_half<true, false>)
+                             : (absgrad ? render_bwd_half<false, true> : render_bwd_half<false, false>);
+    hipLaunchKernelGGL(walk, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats,
+                       final_T, n_contrib, dL_dpix, dL_dinvdepth, reinterpret_cast<float4*>(inst_grads),
+                       reinterpret_cast<uint8_t*>(inst_flag), R, tile_order, wave_order, counters, comp);
 }
 
 }  // namespace
@@ -858,6 +883,16 @@ void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ran
                                           const GsrCompositeDev* comp) {
     launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, splat_grads,
                            inst_grads, inst_flag, R, variant, order_mode, counters, st, comp);
+}
+
+void gsr_launch_render_backward_abs(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
+                                    const float4* splats, const float* final_T, const uint32_t* n_contrib,
+                                    const uint32_t* block_steps, uint32_t* tile_order,
+                                    const float* dL_dpix, const float* dL_dinvdepth, float* inst_grads,
+                                    uint32_t* inst_flag, int64_t R, int order_mode, unsigned long long* counters, hipStream_t st,
+                                    const GsrCompositeDev* comp) {
+    launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, nullptr,
+                           inst_grads, inst_flag, R, 0, order_mode, counters, st, comp, true);
 }
 
 size_t gsr_reduce_units(int64_t R) { return (size_t)((R + RU - 1) / RU); }

@@ -248,16 +248,19 @@ def _backward_scratch(lib, P, num_rendered, device) -> torch.Tensor:
     return torch.empty(_sized("bwd", device, lib.gsr_backward_scratch_bytes(P, num_rendered)), dtype=torch.uint8, device=device)
 
 
-def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device, extra=None) -> Optional[torch.Tensor]:
+def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device, extra=None, absgrad: bool = False) -> Optional[torch.Tensor]:
     """gsr_backward_blend, or with a _lib.CompositeGrads `extra` (alpha-image gradient, per-pixel background, background gradient)
     gsr_backward_blend_composite -> the per-Gaussian 48-byte gradient records [P,12], a view into the backward scratch (None for P == 0,
-    where only the composite call has anything to write: the background gradient)."""
+    where only the composite call has anything to write: the background gradient).  `absgrad`: gsr_backward_blend_abs (`extra` or not) --
+    the same records with the absolute screen-space gradient sums in words 10, 11."""
     lib = _lib.load()
     scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
     rec_ptr = C.c_void_p(0)
     args = (C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(g_color), _ptr(g_depth), _ptr(scratch),
             C.byref(rec_ptr))
-    if extra is None:
+    if absgrad:
+        _lib.check(lib.gsr_backward_blend_abs(*args, None if extra is None else C.byref(extra), _stream_ptr(device)), "gsr_backward_blend_abs")
+    elif extra is None:
         _lib.check(lib.gsr_backward_blend(*args, _stream_ptr(device)), "gsr_backward_blend")
     else:
         _lib.check(lib.gsr_backward_blend_composite(*args, C.byref(extra), _stream_ptr(device)), "gsr_backward_blend_composite")
@@ -265,6 +268,15 @@ def _backward_blend(s, P, fwd: _Forward, g_color, g_depth, device, extra=None) -
         return None
     off = int(rec_ptr.value) - scratch.data_ptr()
     return scratch[off:off + P * 48].view(torch.float32).view(P, 12)
+
+
+def _absgrad_from_records(s, P, records, device) -> torch.Tensor:
+    """gsr_absgrad_from_records: words 10, 11 of the [P,12] records of an `absgrad` blend backward -> means2D_abs[P,3], the units and layout of
+    dL_dmeans2D."""
+    out = torch.empty(P, 3, dtype=torch.float32, device=device)
+    if P > 0:
+        _lib.check(_lib.load().gsr_absgrad_from_records(C.byref(s), P, _ptr(records), _ptr(out), _stream_ptr(device)), "gsr_absgrad_from_records")
+    return out
 
 
 def _gradients(P, device, colors: bool, cov3D: bool, sh_rows, dc: bool, scales: bool, rotations: bool):
@@ -530,7 +542,8 @@ def fuse_sh_adam_into_backward(optimizer, dc_param, rest_param):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None, bg=None, return_alpha=False):
+                raster_settings, tile_rows, grad_sync, dc, viewmatrix=None, projmatrix=None, campos=None, bg=None, return_alpha=False,
+                absgrad=False):
         # viewmatrix / projmatrix / campos / bg: raster_settings' own tensors, passed again so that autograd sees them (camera gradients,
         # gsr_backward_preprocess_camera; background gradient, gsr_backward_blend_composite).  The kernels read them from raster_settings.
         _lib.load()      # (a missing library is reported before anything else)
@@ -566,6 +579,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_sync is not None and (ctx.bg_image or ctx.bg_grad or return_alpha):
             raise GsrError("the alpha image, a per-pixel background and the background gradient are not supported together with grad_sync "
                            "(multi-GPU renderers): detach / broadcast the background and call without return_alpha")
+        # absgrad: the backward also leaves sum over pixels of |per-pixel dL/dmeans2D| in means2D.absgrad (gsr_backward_blend_abs)
+        ctx.absgrad = bool(absgrad)
+        if ctx.absgrad and (means2D is None or not means2D.requires_grad):      # (the tensor's own flag: a render under no_grad is fine)
+            raise ValueError("absgrad=True needs a means2D tensor that requires grad (the reference's screenspace_points): the backward "
+                             "leaves the absolute gradient in its .absgrad attribute")
+        if ctx.absgrad and grad_sync is not None:
+            raise GsrError("absgrad is not supported together with grad_sync (multi-GPU renderers): use the single-GPU rasterizer for it")
+        ctx.means2D_ref = means2D if ctx.absgrad else None      # the caller's own tensor: backward sets its .absgrad
         # the composite entry point only when something beyond the reference's contract is asked for
         composite = bool(return_alpha) or ctx.bg_image or ctx.bg_grad
         keep: list = []
@@ -688,14 +709,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                 fwd = _Forward(geom, binning, img, ctx.num_rendered)
                 cpu_args = _cpu_copy((means3D, radii, col, sc, rot, cov, sh, grad_out_color, rs)) if rs.debug else None
                 try:
-                    if fused_adam is None and not ctx.camera_grad and ctx.grad_sync is None and comp is None:
+                    if fused_adam is None and not ctx.camera_grad and ctx.grad_sync is None and comp is None and not ctx.absgrad:
                         _rasterize_backward(s, P, M, inputs, radii, fwd, g_color, g_depth, grads, device)
                     else:
                         # blend backward -> (multi-GPU: sum of the 48-byte per-Gaussian records across ranks, parallel.py) -> the
                         # per-Gaussian backward that also sums the camera gradient, or steps the two SH tensors in place
-                        records = _backward_blend(s, P, fwd, g_color, g_depth, device, comp)
+                        records = _backward_blend(s, P, fwd, g_color, g_depth, device, comp, ctx.absgrad)
                         if ctx.grad_sync is not None:
                             ctx.grad_sync(records)
+                        if ctx.absgrad:      # gsplat's convention: overwritten by every backward, never accumulated
+                            ctx.means2D_ref.absgrad = _absgrad_from_records(s, P, records, device)
                         if fused_adam is not None:
                             extra = fused_adam.arm()
                         elif ctx.camera_grad:
@@ -709,6 +732,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                         torch.save(cpu_args, "snapshot_bw.dump")
                         print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                     raise
+        if ctx.absgrad and P == 0:
+            ctx.means2D_ref.absgrad = torch.zeros(0, 3, dtype=torch.float32, device=device)
         dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drot = grads
         dL_dopacity = dL_dopacity.view(ctx.op_shape)
         if ctx.dc_mode == "as_sh":      # the DC tensor travelled as the fused [P,1,3] form
@@ -727,7 +752,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if dL_dbg is not None:
             dL_dbg = dL_dbg.reshape(ctx.bg_meta[0]).to(ctx.bg_meta[1])
         return (dL_dmeans3D, dL_dmeans2D if ctx.has_means2D else None, dL_dsh, dL_dcolors if has_col else None, dL_dopacity, dL_dscales, dL_drot,
-                dL_dcov3D if has_cov else None, None, None, None, dL_ddc) + cam_grads + (dL_dbg, None)
+                dL_dcov3D if has_cov else None, None, None, None, dL_ddc) + cam_grads + (dL_dbg, None, None)
 
 
 def _cpu_copy(args):
@@ -735,7 +760,8 @@ def _cpu_copy(args):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, tile_rows: Optional[Tuple[int, int]] = None, grad_sync=None, dc=None, return_alpha: bool = False):
+                        raster_settings, tile_rows: Optional[Tuple[int, int]] = None, grad_sync=None, dc=None, return_alpha: bool = False,
+                        absgrad: bool = False):
     """Functional form.  `grad_sync(records[P,12])`, if given, is called between the blend backward and the
     per-Gaussian backward (multi-GPU: all-reduce of the 48-byte gradient records, parallel.py).
     `tile_rows=(y0, y1)` (extension) restricts binning + blending to that
@@ -746,19 +772,26 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     Alpha image and background (no reference counterpart, include/gsr.h gsr_rasterize_forward_composite): `return_alpha=True` returns
     `(color, radii, invdepth, alpha)` with the differentiable accumulated opacity alpha[1,H,W] = 1 - T_final.  raster_settings.bg may be
     [3] or a per-pixel image [3,H,W]; when it requires grad, backward returns its gradient (with `tile_rows`, the band's contribution).
-    Not available with `grad_sync` (GsrError)."""
+    Not available with `grad_sync` (GsrError).
+    Absolute screen-space gradients (no reference counterpart, include/gsr.h gsr_backward_blend_abs; AbsGS, gsplat's `absgrad`):
+    with `absgrad=True` every backward also sets `means2D.absgrad`, a fresh [P,3] fp32 tensor (overwritten, never accumulated) =
+    (0.5 W sum_p |dL/dpx per pixel|, 0.5 H sum_p |dL/dpy per pixel|, 0) -- the units and layout of means2D.grad, whose signed sums
+    cancel under a large Gaussian over fine detail.  Every gradient is the bits of the same call with absgrad=False.  means2D must
+    require grad (ValueError); not available with `grad_sync` (GsrError); with `tile_rows`, the band's contribution."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, tile_rows, grad_sync, dc, raster_settings.viewmatrix,
-                                     raster_settings.projmatrix, raster_settings.campos, raster_settings.bg, bool(return_alpha))
+                                     raster_settings.projmatrix, raster_settings.campos, raster_settings.bg, bool(return_alpha), bool(absgrad))
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False, absgrad: bool = False):
         """`return_alpha=True` (opt-in, no reference counterpart): the call returns `(color, radii, invdepth, alpha)`, alpha[1,H,W] being the
-        differentiable accumulated opacity 1 - T_final (rasterize_gaussians)."""
+        differentiable accumulated opacity 1 - T_final (rasterize_gaussians).  `absgrad=True` (opt-in, no reference counterpart): every
+        backward also sets `means2D.absgrad`, the absolute screen-space gradient of AbsGS (rasterize_gaussians)."""
         super().__init__()
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
+        self.absgrad = bool(absgrad)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """bool[P]: in front of the near plane (the reference's mark_visible / checkFrustum)."""
@@ -774,7 +807,7 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, getattr(self, "tile_rows", None), None, dc, self.return_alpha)
+                                   self.raster_settings, getattr(self, "tile_rows", None), None, dc, self.return_alpha, self.absgrad)
 
 
     def _tracking_forward(self, means3D, opacities, scales, rotations, cov3D_precomp):

@@ -123,6 +123,8 @@ SIGNATURES = {
     "gsr_rasterize_forward_composite": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 7 + _BUFFERS + [_vp, _vp, _vp, _i32p, C.POINTER(CompositeOut), _vp]),
     "gsr_composite_grad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "gsr_backward_blend_composite": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), C.POINTER(CompositeGrads), _vp]),
+    "gsr_backward_blend_abs": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 6 + [C.POINTER(C.c_void_p), C.POINTER(CompositeGrads), _vp]),
+    "gsr_absgrad_from_records": (C.c_int, [_RS, C.c_int, _vp, _vp, _vp]),
     "gsr_contribution_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "gsr_contribution_stats": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.POINTER(ContribOut), _vp]),
     "gsr_pixel_probe": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 3 + [C.POINTER(PixelProbeOut), _vp]),

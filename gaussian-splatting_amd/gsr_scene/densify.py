@@ -204,7 +204,7 @@ def reset_opacity(optimizer, cap: float = 0.01, opacity_activation=torch.sigmoid
     return p
 
 
-def attach(gaussians, fused_adam: bool = True):
+def attach(gaussians, fused_adam: bool = True, absgrad: bool = False):
     """Binds this module's density control to an instance of the reference's `scene.gaussian_model.GaussianModel` (duck-typed: any object with
     its attributes), so that the UNCHANGED caller reaches it through the method calls it already makes (train.py:164-174):
 
@@ -221,6 +221,9 @@ def attach(gaussians, fused_adam: bool = True):
     fused_adam (default): when `gaussians.optimizer` is a plain `torch.optim.Adam` over HIP tensors -- train.py's default `optimizer_type`
     (scene/gaussian_model.py:193-199) -- it is replaced by `gsr_optim.FusedAdam` with the SAME param groups and state (one HIP kernel for the
     six tensors instead of torch's foreach chain; same state-dict layout, so `capture()` / `restore()` and the density control keep working).
+    absgrad (opt-in, AbsGS): add_densification_stats accumulates the norm of `viewspace_point_tensor.absgrad` -- the absolute screen-space
+    gradient that `GaussianRasterizer(settings, absgrad=True)` leaves on the tensor at every backward -- instead of that of `.grad`; the
+    threshold it is compared with (`densify_grad_threshold`) has to be raised accordingly.
     Returns the instance."""
     import types
     opt = getattr(gaussians, "optimizer", None)
@@ -236,7 +239,13 @@ def attach(gaussians, fused_adam: bool = True):
         return DensifyStats(self.xyz_gradient_accum, self.denom, self.max_radii2D)
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
-        _stats(self).add(viewspace_point_tensor.grad, update_filter, None)      # (max_radii2D is updated by the caller itself, train.py:166)
+        g = viewspace_point_tensor.grad
+        if absgrad:
+            g = getattr(viewspace_point_tensor, "absgrad", None)
+            if g is None:
+                raise RuntimeError("attach(absgrad=True): viewspace_point_tensor has no .absgrad -- construct the rasterizer with "
+                                   "GaussianRasterizer(raster_settings, absgrad=True) and call backward() first")
+        _stats(self).add(g, update_filter, None)      # (max_radii2D is updated by the caller itself, train.py:166)
 
     def densify_and_prune_(self, max_grad, min_opacity, extent, max_screen_size, radii):
         params, new_stats, _tmp = densify_and_prune(self.optimizer, _stats(self), max_grad, min_opacity, extent, max_screen_size,

@@ -136,7 +136,7 @@ int gsr_rasterize_forward(const GsrRasterSettings* settings, int P, int M,
  *   bwd_scratch: caller-owned scratch of gsr_backward_scratch_bytes(P, num_rendered) bytes (per-instance
  *   gradient records, the emission-order inverse map and the per-Gaussian 2-D gradient record).
  *   If splat_grads_out is non-NULL it receives the device address (inside bwd_scratch) of the per-Gaussian
- *   record [P,12] = [dpx,dpy,dA,dB,dC,dopacity,dr,dg,db,dinvdepth,0,0] -- the 48-byte payload that is
+ *   record [P,12] = [dpx,dpy,dA,dB,dC,dopacity,dr,dg,db,dinvdepth,0,0] (words 10, 11: gsr_backward_blend_abs) -- the 48-byte payload that is
  *   reduce-scattered between GPUs when the screen is sharded.
  */
 int gsr_rasterize_backward(const GsrRasterSettings* settings, int P, int M, int32_t num_rendered,
@@ -253,6 +253,36 @@ int gsr_backward_blend_composite(const GsrRasterSettings* settings, int P, int32
                                  const float* dL_dout_color, const float* dL_dout_invdepth,
                                  void* bwd_scratch, float** splat_grads_out,
                                  const GsrCompositeGrads* extra, void* stream);
+
+/*
+ * Absolute screen-space gradients (no reference counterpart; the densification signal of AbsGS, gsplat's `absgrad`): the blend backward
+ * that also returns, per Gaussian, the sum over pixels of the ABSOLUTE per-pixel gradient of its 2-D centre -- the signed sums of words
+ * 0, 1 cancel where a large Gaussian covers fine detail, and density control then never splits it.
+ * For Gaussian g and every pixel p of the rendered band at which the blend backward takes g -- the hard masks of the signed gradient,
+ * nothing re-tested and nothing new: list position < n_contrib[p], power <= 0, alpha >= 1/255 -- with dx = mean2D.x - p.x,
+ * dy = mean2D.y - p.y, the conic (A, B, C) and
+ *   m_gp = opacity * G * dL/dalpha_gp      the backward's own m, straight through the 0.99 cap, including the background, alpha-image and
+ *                                          inverse-depth terms when present,
+ *   abs_x[g] = sum_p | m_gp (A dx + B dy) |        abs_y[g] = sum_p | m_gp (C dy + B dx) |
+ * Products and sums are fp32, the summation order is fixed (two runs give the same bits), there are no atomics.
+ * gsr_backward_blend_abs takes the arguments of gsr_backward_blend_composite, except that `extra` may be NULL (then it is gsr_backward_blend
+ * with the two sums).  In the [P,12] records abs_x, abs_y are words 10, 11, in pixel units like words 0, 1; words 0 to 9 are the bits
+ * gsr_backward_blend / gsr_backward_blend_composite write for the same inputs, and so is everything `extra` returns.  Rows without a
+ * contributing pixel (culled Gaussians included) are zero.  With a band of tile rows the two words are the band's contribution; sums of
+ * non-negative terms over disjoint bands add up to the full frame's, so the records stay correct under the all-reduce / reduce-scatter
+ * of the sharded modes.  Every state gsr_backward_blend accepts is accepted (the record entry points' included); P == 0 or
+ * num_rendered == 0 gives zero rows.  bwd_scratch is that of gsr_backward_blend (gsr_backward_scratch_bytes).  Builds with the
+ * measurement variants (-DGSR_AB_VARIANTS) and a render_bwd_variant other than the default return GSR_ERR_UNSUPPORTED.
+ * gsr_absgrad_from_records converts records into means2D_abs[P,3] = (0.5 W abs_x, 0.5 H abs_y, 0): the units and layout of
+ * dL_dmeans2D, so it drops into gsr_density_stats unchanged.  Every row is overwritten; splat_grads must be 8-byte aligned.
+ */
+int gsr_backward_blend_abs(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                           const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                           const float* dL_dout_color, const float* dL_dout_invdepth,
+                           void* bwd_scratch, float** splat_grads_out,
+                           const GsrCompositeGrads* extra /* may be NULL */, void* stream);
+int gsr_absgrad_from_records(const GsrRasterSettings* settings, int P, const float* splat_grads,
+                             float* means2D_abs /* [P,3] */, void* stream);
 
 /*
  * Per-Gaussian blend-weight statistics (no reference counterpart): what each Gaussian GAVE to the image of one forward -- the
