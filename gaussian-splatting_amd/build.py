@@ -6,7 +6,8 @@ Translation units and their flags:
   preprocess.hip   -ffp-contract=off   (bit-exact radii / tile counts, see csrc/gsr_math.h)
   sort.hip, depthsort.hip, binning.hip (integer)
   render_fwd.hip, render_bwd.hip,
-  contrib.hip, probe.hip, absgrad.hip  (FMA contraction allowed; image tolerance 1e-5; what the four must compute identically -- box
+  contrib.hip, probe.hip, absgrad.hip,
+  features.hip                         (FMA contraction allowed; image tolerance 1e-5; what they must compute identically -- box
                                         test, exponent / alpha -- is csrc/gsr_blend.h, their wave reductions csrc/gsr_wave.h)
   gsr_api.cpp                          (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
@@ -47,6 +48,7 @@ UNITS = [
     ("contrib.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("probe.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("absgrad.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
+    ("features.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("adam.hip", ["-ffp-contract=off"]),
     # no SLP vectorisation: the auto-packed v_pk_fma_f32 and the v_mov shuffles that assemble their operand pairs cost more
     # issue slots than the scalar FMAs they replace (forward 60.2 -> 55.3 us on one box); the per-Gaussian kernels were

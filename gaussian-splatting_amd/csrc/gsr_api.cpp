@@ -1226,6 +1226,68 @@ int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_render
     return GSR_OK;
 }
 
+// the checks gsr_render_features and gsr_render_features_backward share (those of gsr_pixel_probe, plus the channel count)
+static int feature_args(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                        const void* image_buffer, int C, GsrCamDev& cam) {
+    int rc = make_cam(settings, 0, cam);
+    if (rc != GSR_OK) return rc;
+    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
+    if (C < 1 || C > GSR_MAX_FEATURE_CHANNELS) return fail(GSR_ERR_INVALID_ARG, "C (feature channels) must be inside [1, 1024]");
+    if (P > 0 && num_rendered > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
+    return GSR_OK;
+}
+
+int gsr_render_features(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                        const void* image_buffer, const float* features, int C, float* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GsrCamDev cam;
+    int rc = feature_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, C, cam);
+    if (rc != GSR_OK) return rc;
+    if (P > 0 && (!features || !out)) return fail(GSR_ERR_INVALID_ARG, "features / out are NULL");
+    const int64_t R = num_rendered;
+    if (P == 0 || R == 0) {      // no state to read: zeros over the band
+        if (out) gsr_launch_render_features_defaults(cam, C, out, st);
+        HIP_OK(hipGetLastError());
+        return GSR_OK;
+    }
+    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
+    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
+    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
+    const int list_buf = list_buffer_index(cam.gx * cam.gy);
+    gsr_launch_render_features(cam, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, features, C, out, st);
+    STAGE_CHECK("render features");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+size_t gsr_feature_grad_scratch_bytes(int P, int64_t R, int C) { (void)P; return gsr_carve_feature_grad(nullptr, R, C < 1 ? 1 : C).bytes; }
+
+int gsr_render_features_backward(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
+                                 const void* binning_buffer, const void* image_buffer, const float* dL_dout, int C, void* scratch,
+                                 float* dL_dfeatures, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GsrCamDev cam;
+    int rc = feature_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, C, cam);
+    if (rc != GSR_OK) return rc;
+    if (P > 0 && (!dL_dout || !dL_dfeatures)) return fail(GSR_ERR_INVALID_ARG, "dL_dout / dL_dfeatures are NULL");
+    const int64_t R = num_rendered;
+    if (R > 0 && !scratch) return fail(GSR_ERR_INVALID_ARG, "scratch is NULL (gsr_feature_grad_scratch_bytes)");
+    if (((uintptr_t)scratch) & 15) return fail(GSR_ERR_INVALID_ARG, "feature gradient scratch must be 16-byte aligned");
+    // every row is written: Gaussians without instances keep these zeros
+    if (P > 0) HIP_OK(hipMemsetAsync(dL_dfeatures, 0, (size_t)P * (size_t)C * sizeof(float), st));
+    if (P == 0 || R == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
+    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
+    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
+    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
+    const int list_buf = list_buffer_index(cam.gx * cam.gy);
+    gsr_launch_render_features_backward(cam, P, R, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, g.vals[depth_order_buffer_index()], g.offsets,
+                                        dL_dout, C, gsr_carve_feature_grad((char*)scratch, R, C), dL_dfeatures, st);
+    STAGE_CHECK("render features backward");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 // gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera
 static int backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
                                const float* colors_precomp, const float* opacities, const float* scales,

@@ -355,6 +355,19 @@ void gsr_launch_pixel_probe(const GsrCamDev& cam, const uint2* ranges, const uin
                             const GsrPixelProbeOut& out, hipStream_t st);
 void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOut& out, hipStream_t st);
 
+// features.hip: N-channel per-Gaussian features blended with a finished forward's weights (gsr_render_features / _backward).  The forward writes every
+// in-band, in-image pixel of out[C,H,W], zeros included; _defaults fills the band's rows of every plane without reading any state (the call with P == 0
+// or num_rendered == 0).  The backward's scratch has contrib.hip's shape (GsrContribScratch, gsr_carve_feature_grad: one slot record per (8x8 block of the
+// tile, instance) holding the channel sums of one group, slot-major, and a flag word per instance; 64-bit offsets), reused by every channel group of a
+// call; rows of dL_dfeatures[P,C] of Gaussians without instances are not touched (the caller zeroes the array).
+GsrContribScratch gsr_carve_feature_grad(char* base, int64_t R, int C);
+void gsr_launch_render_features(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
+                                const float* features, int C, float* out, hipStream_t st);
+void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out, hipStream_t st);
+void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list,
+                                         const float4* splats, const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets,
+                                         const float* dL_dout, int C, const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st);
+
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                      int step, hipStream_t st);

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import GsrError, GsrRasterSettings, RESIZE_FN  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam", "rasterize_gaussians", "GsrError",
-           "ContributionStats", "contribution_stats", "PixelProbe", "pixel_probe"]
+           "ContributionStats", "contribution_stats", "PixelProbe", "pixel_probe", "render_features"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -462,6 +462,78 @@ def pixel_probe(rendered: torch.Tensor, threshold: float = 0.5) -> PixelProbe:
         return _pixel_probe(s, st.P, st.fwd, threshold, int(rs.image_height), int(rs.image_width), st.device)
 
 
+MAX_FEATURE_CHANNELS = 1024      # GSR_MAX_FEATURE_CHANNELS of include/gsr.h
+
+
+def _feature_rows(features, P: int, device) -> torch.Tensor:
+    """`features` as the C ABI takes it: [P,C] float32 contiguous on the state's device, 1 <= C <= MAX_FEATURE_CHANNELS."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2:
+        raise GsrError(f"features must be a tensor of shape [P, C], got {list(features.shape) if isinstance(features, torch.Tensor) else type(features)}")
+    if int(features.shape[0]) != P:
+        raise GsrError(f"features has {int(features.shape[0])} rows, the rendered state {P} Gaussians")
+    if not 1 <= int(features.shape[1]) <= MAX_FEATURE_CHANNELS:
+        raise GsrError(f"features must have between 1 and {MAX_FEATURE_CHANNELS} channels, got {int(features.shape[1])}")
+    if features.device != device:
+        raise GsrError(f"features lives on {features.device}, the rendered state on {device}")
+    return features
+
+
+class _RenderFeatures(torch.autograd.Function):
+    """F[C,H,W] = sum_g w f[g] on the state of a finished tracking forward (gsr_render_features), differentiable in `features` only
+    (gsr_render_features_backward).  It keeps its OWN references to the three state tensors, so its backward does not depend on the frame's
+    graph; without a gradient to compute it keeps nothing."""
+
+    @staticmethod
+    def forward(ctx, features, geom, binning, img, num_rendered, raster_settings, tile_rows):
+        lib = _lib.load()
+        device = features.device
+        P, Cn = int(features.shape[0]), int(features.shape[1])
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        f = _f32c(features.detach())
+        out = torch.zeros(Cn, H, W, dtype=torch.float32, device=device)      # (with `tile_rows` the library leaves pixels outside the band untouched)
+        keep: list = []
+        with torch.cuda.device(device):
+            s = _make_settings(raster_settings, keep, tile_rows, bg_image=True)
+            _lib.check(lib.gsr_render_features(C.byref(s), P, num_rendered, _ptr(geom), _ptr(binning), _ptr(img), _ptr(f), Cn, _ptr(out),
+                                               _stream_ptr(device)), "gsr_render_features")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(geom, binning, img)
+            ctx.num_rendered, ctx.raster_settings, ctx.tile_rows, ctx.shape, ctx.dtype = num_rendered, raster_settings, tile_rows, (P, Cn), features.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        geom, binning, img = ctx.saved_tensors
+        P, Cn = ctx.shape
+        device = grad_out.device
+        g = _f32c(grad_out)
+        grad = torch.empty(P, Cn, dtype=torch.float32, device=device)
+        keep: list = []
+        with torch.cuda.device(device):
+            s = _make_settings(ctx.raster_settings, keep, ctx.tile_rows, bg_image=True)
+            scratch = torch.empty(_sized("contrib", device, lib.gsr_feature_grad_scratch_bytes(P, ctx.num_rendered, Cn)), dtype=torch.uint8, device=device)
+            _lib.check(lib.gsr_render_features_backward(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img), _ptr(g), Cn,
+                                                        _ptr(scratch), _ptr(grad), _stream_ptr(device)), "gsr_render_features_backward")
+        return grad.to(ctx.dtype), None, None, None, None, None, None
+
+
+def render_features(rendered: torch.Tensor, features: torch.Tensor) -> torch.Tensor:
+    """-> F[C,H,W] = sum_g w_gp features[g,c]: N-channel per-Gaussian features (language / semantic fields, distillation heads, label votes) blended
+    with the weights w = alpha * T of a frame that has ALREADY been rendered (no reference counterpart; include/gsr.h gsr_render_features).
+    `rendered` and the state it is read from are `contribution_stats`'s: any tensor computed from one rasterizer call's outputs with gradients
+    enabled, before that call's `backward()` frees the state (or with `retain_graph=True`); no second forward, whatever C is.  `features` is
+    [P,C], 1 <= C <= 1024.  There is NO background term and no normalisation: compose with the alpha image of `return_alpha=True`.
+    Differentiable in `features` ONLY: geometry and opacity are constants of the frame already rendered, so no gradient reaches means3D,
+    scales, rotations or opacities through F (train those through the colour render).  The backward keeps its own references to the state: it
+    still runs after the frame's own `backward()`.  Rows of Gaussians that contribute nowhere never reach the image and get exact zero
+    gradients.  With `tile_rows`, pixels outside the band are 0 and the gradient is the band's.  Two calls give the same bits, and channel c has
+    the bits of a call on column c alone."""
+    st = _saved_state(rendered, "render_features", "features")
+    features = _feature_rows(features, st.P, st.device)
+    return _RenderFeatures.apply(features, st.fwd.geom, st.fwd.binning, st.fwd.img, st.fwd.num_rendered, st.settings, st.tile_rows)
+
+
 def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
     """gsr_mark_visible -> bool[P]: in front of the near plane (the reference's checkFrustum with prefiltered = False)."""
     lib = _lib.load()
@@ -852,6 +924,19 @@ class GaussianRasterizer(nn.Module):
         with torch.no_grad(), torch.cuda.device(device):
             s, P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
             return _pixel_probe(s, P, fwd, threshold, int(rs.image_height), int(rs.image_width), device), radii
+
+    def features(self, means3D, opacities, features, scales=None, rotations=None, cov3D_precomp=None):
+        """-> (F[C,H,W], radii[P]): `render_features` for this camera without a render of one's own to hand (no reference counterpart): runs a
+        tracking forward with zero colours under no_grad, honours `tile_rows`, then blends `features` [P,C] with its weights.  Differentiable in
+        `features` only: no gradient reaches the geometry or the opacities through F."""
+        _lib.load()
+        _require_cuda(means3D, "means3D")
+        device = means3D.device
+        features = _feature_rows(features, int(means3D.shape[0]), device)
+        with torch.no_grad(), torch.cuda.device(device):
+            _s, _P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
+        return _RenderFeatures.apply(features, fwd.geom, fwd.binning, fwd.img, fwd.num_rendered, self.raster_settings,
+                                     getattr(self, "tile_rows", None)), radii
 
 
 class SparseGaussianAdam(torch.optim.Adam):

@@ -358,6 +358,41 @@ int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_render
                     const GsrPixelProbeOut* out, void* stream);
 
 /*
+ * N-channel per-Gaussian features blended with the weights of a forward that has ALREADY run (no reference counterpart): language / semantic
+ * feature fields, distillation heads, label lifting -- any number of channels on the geometry of one frame, without one forward and one blend
+ * backward per three channels.  Read from the state of gsr_contribution_stats / gsr_pixel_probe: gsr_rasterize_forward /
+ * gsr_rasterize_forward_composite run with no_backward == 0, the same settings, the same buffers, num_rendered as returned.  The states of the
+ * record entry points (from_splats / from_packed / from_segments) are not supported.
+ * Conventions, those two functions': Gaussian g contributes to pixel p exactly when the forward blended it there -- its entry is valid
+ * (power <= 0 and alpha >= 1/255, alpha capped at 0.99) and its list position is <= n_contrib[p]; n_contrib is the authority on termination
+ * (T < 1e-4 is not re-tested); w_gp = alpha_gp * T_gp is the forward's blend weight.
+ *   gsr_render_features            out[c,p] = sum_g w_gp features[g,c], fp32 in list order.  NO background term and no normalisation: compose
+ *                                  with the alpha image of gsr_rasterize_forward_composite (1 - alpha is the weight of a background).
+ *   gsr_render_features_backward   dL_dfeatures[g,c] = sum_p w_gp dL_dout[c,p]: the gradient with respect to `features` ONLY.  Geometry and
+ *                                  opacity are constants of the frame already rendered; gradients to them through `out` are not computed.
+ * features / dL_dfeatures are [P,C] row-major, out / dL_dout planar [C,H,W], 1 <= C <= GSR_MAX_FEATURE_CHANNELS.  Rows of `features` of
+ * Gaussians that contribute nowhere (culled, hidden) are never multiplied into the image -- they may hold anything -- and their rows of
+ * dL_dfeatures are exact zeros; every one of the P rows is written.  Every pixel of the band inside the image is written (zeros without a
+ * contributor); with a band of tile rows (tile_y0 / tile_y1) pixels of `out` outside the band are not touched, dL_dout is read inside the band
+ * only and dL_dfeatures is the band's contribution.  P == 0 or num_rendered == 0: zeros over the band / zero rows, and the state buffers are
+ * not read (they may be NULL).  Bit-reproducible: no atomics, every sum in a fixed order; channel c of a C-channel call has the bits of a
+ * 1-channel call on column c alone.
+ * `scratch`: device memory of gsr_feature_grad_scratch_bytes(P, num_rendered, C) bytes, 16-byte aligned, contents undefined before and after;
+ * one region reused by every channel group of a call: 68, 132 or 260 bytes per instance for C <= 4, <= 8 or more, whatever C is beyond that.  NULL settings, negative P / num_rendered, C outside the range, NULL features / out (dL_dout /
+ * dL_dfeatures) with P > 0, a NULL scratch with num_rendered > 0, or NULL state buffers with P > 0 and num_rendered > 0 are
+ * GSR_ERR_INVALID_ARG.
+ */
+#define GSR_MAX_FEATURE_CHANNELS 1024
+int gsr_render_features(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                        const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                        const float* features /* [P,C] */, int C, float* out /* [C,H,W] */, void* stream);
+size_t gsr_feature_grad_scratch_bytes(int P, int64_t R, int C);
+int gsr_render_features_backward(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                                 const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                 const float* dL_dout /* [C,H,W] */, int C, void* scratch,
+                                 float* dL_dfeatures /* [P,C] */, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
