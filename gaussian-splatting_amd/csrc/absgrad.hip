@@ -99,11 +99,11 @@ absgrad_from_records(int P, float half_w, float half_h, const float* __restrict_
 
 }  // namespace
 
-void gsr_launch_absgrad_reduce(int P, int64_t R, const uint32_t* order, const uint32_t* offsets, const float* inst_grads, const uint32_t* inst_flag,
-                               float* splat_grads, hipStream_t st) {
+void gsr_launch_absgrad_reduce(int P, int64_t R, const GsrSavedFrame& f, const float* inst_grads, const uint32_t* inst_flag, float* splat_grads,
+                               hipStream_t st) {
     if (P <= 0 || R <= 0) return;
-    hipLaunchKernelGGL(absgrad_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, R, order, offsets, reinterpret_cast<const float4*>(inst_grads), inst_flag,
-                       splat_grads);
+    hipLaunchKernelGGL(absgrad_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, R, f.order, f.offsets, reinterpret_cast<const float4*>(inst_grads),
+                       inst_flag, splat_grads);
 }
 
 void gsr_launch_absgrad_from_records(int P, int W, int H, const float* splat_grads, float* means2D_abs, hipStream_t st) {

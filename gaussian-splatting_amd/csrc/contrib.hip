@@ -217,16 +217,15 @@ GsrContribScratch gsr_carve_contrib(char* base, int64_t R) {
     return w;
 }
 
-void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list, const float4* splats,
-                                   const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets, const float* pixel_weight,
+void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* pixel_weight,
                                    const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count, int accumulate,
                                    hipStream_t st) {
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0 || P <= 0 || R <= 0) return;
     (void)hipMemsetAsync(w.flags, 0, (size_t)R * 4, st);
     const int groups = (n_band_tiles + 7) / 8;
-    hipLaunchKernelGGL(contrib_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats, n_contrib, pixel_weight,
-                       w.slots, reinterpret_cast<uint8_t*>(w.flags), R);
-    hipLaunchKernelGGL(contrib_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, R, order, offsets, (const float4*)w.slots, (const uint32_t*)w.flags,
-                       weight_sum, weight_max, pixel_count, accumulate);
+    hipLaunchKernelGGL(contrib_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib,
+                       pixel_weight, w.slots, reinterpret_cast<uint8_t*>(w.flags), R);
+    hipLaunchKernelGGL(contrib_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, R, f.order, f.offsets, (const float4*)w.slots,
+                       (const uint32_t*)w.flags, weight_sum, weight_max, pixel_count, accumulate);
 }

@@ -416,10 +416,9 @@ GsrContribScratch gsr_carve_feature_grad(char* base, int64_t R, int C) {
 }
 
 void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out, hipStream_t st) {
-    const int t0 = cam.tile_y0 * GSR_TILE, t1 = cam.tile_y1 * GSR_TILE;
-    const int r0 = t0 < cam.H ? t0 : cam.H, r1 = t1 < cam.H ? t1 : cam.H;
-    if (r1 <= r0) return;
-    const size_t plane = (size_t)cam.W * cam.H, first = (size_t)r0 * cam.W, pixels = (size_t)(r1 - r0) * cam.W;
+    const GsrBandRows band = gsr_band_rows(cam);
+    const size_t plane = (size_t)cam.W * cam.H, first = band.first, pixels = band.pixels;
+    if (pixels == 0) return;
     if (pixels == plane) {      // the whole frame: the planes are one contiguous range
         (void)hipMemsetAsync(out, 0, plane * (size_t)C * sizeof(float), st);
         return;
@@ -427,25 +426,23 @@ void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out
     for (int c = 0; c < C; ++c) (void)hipMemsetAsync(out + (size_t)c * plane + first, 0, pixels * sizeof(float), st);
 }
 
-void gsr_launch_render_features(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
-                                const float* features, int C, float* out, hipStream_t st) {
+void gsr_launch_render_features(const GsrCamDev& cam, const GsrSavedFrame& f, const float* features, int C, float* out, hipStream_t st) {
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0) return;
     const int groups = (n_band_tiles + 7) / 8;
     const bool vec4 = (C % 4 == 0) && (((uintptr_t)features) & 15) == 0;
     for (int c0 = 0; c0 < C; c0 += FEAT_G) {
         if (vec4)
-            hipLaunchKernelGGL(feature_walk<true>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats, n_contrib,
+            hipLaunchKernelGGL(feature_walk<true>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib,
                                features, C, c0, out);
         else
-            hipLaunchKernelGGL(feature_walk<false>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats, n_contrib,
+            hipLaunchKernelGGL(feature_walk<false>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib,
                                features, C, c0, out);
     }
 }
 
-void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list,
-                                         const float4* splats, const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets,
-                                         const float* dL_dout, int C, const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st) {
+void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* dL_dout, int C,
+                                         const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st) {
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0 || P <= 0 || R <= 0) return;
     const int groups = (n_band_tiles + 7) / 8;
@@ -453,9 +450,9 @@ void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R,
         const int nb = feature_grad_nb(C - c0);
         (void)hipMemsetAsync(w.flags, 0, (size_t)R * 4, st);
 #define GSR_FEATURE_GRAD_GROUP(NB)                                                                                                                  \
-        hipLaunchKernelGGL(feature_grad_walk<NB>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats, n_contrib,     \
-                           dL_dout, C, c0, w.slots, reinterpret_cast<uint8_t*>(w.flags), R);                                                        \
-        hipLaunchKernelGGL(feature_grad_reduce<NB>, dim3((P + 63) / 64), dim3(64), 0, st, P, R, order, offsets, (const float4*)w.slots,             \
+        hipLaunchKernelGGL(feature_grad_walk<NB>, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats,          \
+                           f.n_contrib, dL_dout, C, c0, w.slots, reinterpret_cast<uint8_t*>(w.flags), R);                                           \
+        hipLaunchKernelGGL(feature_grad_reduce<NB>, dim3((P + 63) / 64), dim3(64), 0, st, P, R, f.order, f.offsets, (const float4*)w.slots,         \
                            (const uint32_t*)w.flags, dL_dfeatures, C, c0)
         if (nb == 4) { GSR_FEATURE_GRAD_GROUP(4); }
         else if (nb == 2) { GSR_FEATURE_GRAD_GROUP(2); }

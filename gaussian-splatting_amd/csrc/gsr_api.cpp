@@ -549,11 +549,40 @@ struct EventPair {
     }
 };
 
-// Which ping-pong buffer holds the depth order is a pure function of the build (3 passes of 9 bits -> vals[1]); the 32-bit
-// fallback sort (4 passes -> vals[0]) copies its result there, so the backward finds it without any state.
+// THE invariant between a forward and every call that reads its buffers back: which ping-pong buffer holds the depth order and which the sorted
+// list is a pure function of the build and of the frame geometry (never of a run-time option or of the frame's content), so a reader finds the
+// forward's results without any state passed between the two calls.
+//   depth order: 3 passes of 9 bits -> vals[1]; the 32-bit fallback sort (4 passes -> vals[0]) copies its result there.
+//   sorted list: <= 65536 tiles: vals[0] (the fused sort writes it; the legacy LSD sort takes 2 passes); more: 3 LSD passes -> vals[1].
+// bin_and_render puts the depth order where depth_order_buffer_index says; its tile sort ends in the buffer list_buffer_index derives from the
+// same pass plan.  saved_frame is the only other caller of either function.
 static int depth_order_buffer_index() {
     int pb[8];
     return gsr_sort_plan(GSR_DEPTH_KEY_BITS, GSR_DEPTH_DIGIT_BITS, pb) & 1;
+}
+static int list_buffer_index(int n_tiles) {
+    if (n_tiles <= 65536) return 0;
+    int pb[8];
+    return gsr_sort_plan(bits_for((uint32_t)n_tiles), GSR_TILE_DIGIT_BITS, pb) & 1;
+}
+
+// The view of a finished forward's three buffers (cam: W, H, gx, gy are read).  Any buffer may be NULL: its pointers are NULL then, and the entry
+// points' own checks decide what they need.  point_list is also NULL for R <= 0 (nothing was binned: the binning buffer may not even exist).
+static GsrSavedFrame saved_frame(const GsrCamDev& cam, int P, int64_t R, const void* geom_buffer, const void* binning_buffer, const void* image_buffer) {
+    const GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
+    const GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
+    GsrSavedFrame f;
+    f.ranges = im.ranges;
+    f.point_list = (binning_buffer && R > 0) ? gsr_carve_binning((char*)binning_buffer, R).vals[list_buffer_index(cam.gx * cam.gy)] : nullptr;
+    f.splats = g.splats;
+    f.final_T = im.final_T;
+    f.n_contrib = im.n_contrib;
+    f.block_steps = im.block_steps;
+    f.tile_order = im.tile_order;
+    f.order = g.vals[depth_order_buffer_index()];
+    f.offsets = g.offsets;
+    f.tiles = g.tiles;
+    return f;
 }
 
 // Host side of the R read-back: spin on the mapped word.  ADVICE r02: in training the host runs far ahead of the GPU, so the
@@ -1035,15 +1064,6 @@ int gsr_route_return(int P, int n_bands, const int64_t* band_offsets, const int3
     return GSR_OK;
 }
 
-// Which ping-pong buffer holds the sorted list / the depth order is a pure function of the frame geometry (never of a
-// run-time option), so the backward finds the forward's results without any state passed between the two calls:
-// <= 65536 tiles: vals[0] (fused sort writes it; the legacy LSD sort takes 2 passes); more: 3 LSD passes -> vals[1].
-static int list_buffer_index(int n_tiles) {
-    if (n_tiles <= 65536) return 0;
-    int pb[8];
-    return gsr_sort_plan(bits_for((uint32_t)n_tiles), GSR_TILE_DIGIT_BITS, pb) & 1;
-}
-
 size_t gsr_composite_grad_scratch_bytes(int width, int height) {
     if (width <= 0 || height <= 0) return 0;
     return gsr_bg_grad_blocks((int64_t)width * height) * 3 * sizeof(double);
@@ -1074,22 +1094,20 @@ static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_
             return fail(GSR_ERR_INVALID_ARG, "dL_dbg_image / dL_dbg need dL_dout_color and the image buffer");
     }
     if (bg_grad) {
-        // every pixel of the band, also those no Gaussian reaches; P == 0: the forward kept no state and T_final = 1 everywhere
-        const float* final_T = P > 0 ? gsr_carve_image((char*)image_buffer, cam.W, cam.H).final_T : nullptr;
-        const int row0 = cam.tile_y0 * GSR_TILE < cam.H ? cam.tile_y0 * GSR_TILE : cam.H;
-        const int row1 = cam.tile_y1 * GSR_TILE < cam.H ? cam.tile_y1 * GSR_TILE : cam.H;
+        // every pixel of the band, also those no Gaussian reaches; P == 0: the forward kept no state and T_final = 1 everywhere.  (Only the image
+        // buffer has been checked so far: the view's other pointers may be NULL here and are not looked at.)
+        const float* final_T = P > 0 ? saved_frame(cam, P, num_rendered, geom_buffer, binning_buffer, image_buffer).final_T : nullptr;
+        const GsrBandRows band = gsr_band_rows(cam);
         StageTimer t(GSR_STAGE_RENDER_BWD, st);
-        gsr_launch_bg_grad((int64_t)cam.W * cam.H, cam.W, row0, row1, final_T, dL_dout_color, extra->dL_dbg_image, extra->dL_dbg,
+        gsr_launch_bg_grad((int64_t)cam.W * cam.H, cam.W, band.row0, band.row1, final_T, dL_dout_color, extra->dL_dbg_image, extra->dL_dbg,
                            (double*)extra->scratch, st);
     }
     if (P == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
     if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dout_color || !bwd_scratch)
         return fail(GSR_ERR_INVALID_ARG, "state buffers / dL_dout_color / bwd_scratch are NULL");
     const GsrCompositeDev* compp = (comp.bg_image || comp.dL_dalpha) ? &comp : nullptr;
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrBinning b = gsr_carve_binning((char*)binning_buffer, num_rendered);
-    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
-    const int list_buf = num_rendered > 0 ? list_buffer_index(cam.gx * cam.gy) : 0;
+    GsrSavedFrame f = saved_frame(cam, P, num_rendered, geom_buffer, binning_buffer, image_buffer);
+    if (!g_bwd_heavy_first) f.tile_order = nullptr;      // tiles in index order
     GsrBwdScratch w = gsr_carve_bwd((char*)bwd_scratch, P, num_rendered);
     float* sg = w.splat_grads;
     if (splat_grads_out) *splat_grads_out = sg;
@@ -1097,27 +1115,22 @@ static int backward_blend(const GsrRasterSettings* settings, int P, int32_t num_
         if (g_render_bwd_variant == 1 || num_rendered <= 0) {
             HIP_OK(hipMemsetAsync(sg, 0, (size_t)P * 12 * sizeof(float), st));
             if (num_rendered > 0)
-                gsr_launch_render_backward(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps, nullptr,
+                gsr_launch_render_backward(cam, f.ranges, f.point_list, f.splats, f.final_T, f.n_contrib, f.block_steps, nullptr,
                                            dL_dout_color, dL_dout_invdepth, sg, nullptr, nullptr, num_rendered, 1, 0, nullptr, st);
         } else if (absgrad) {
-            gsr_launch_render_backward_abs(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
-                                           g_bwd_heavy_first ? im.tile_order : nullptr, dL_dout_color, dL_dout_invdepth, w.inst_grads, w.inst_flag,
-                                           num_rendered, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st, compp);
+            gsr_launch_render_backward_abs(cam, f, dL_dout_color, dL_dout_invdepth, w.inst_grads, w.inst_flag, num_rendered, g_bwd_heavy_first,
+                                           g_count_on ? counters_for_current_device() : nullptr, st, compp);
         } else {
             // (the flag words of the instances are cleared by the launcher: in the plan kernel's launch, or with a fill)
-            gsr_launch_render_backward_composite(cam, im.ranges, b.vals[list_buf], g.splats, im.final_T, im.n_contrib, im.block_steps,
-                                       g_bwd_heavy_first ? im.tile_order : nullptr,
-                                       dL_dout_color, dL_dout_invdepth, nullptr, w.inst_grads, w.inst_flag, num_rendered,
-                                       g_render_bwd_variant, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st, compp);
+            gsr_launch_render_backward_composite(cam, f, dL_dout_color, dL_dout_invdepth, nullptr, w.inst_grads, w.inst_flag, num_rendered,
+                                                 g_render_bwd_variant, g_bwd_heavy_first, g_count_on ? counters_for_current_device() : nullptr, st, compp);
         }
     }
     STAGE_CHECK("render backward blend");
     if (g_render_bwd_variant != 1 && num_rendered > 0) {
         StageTimer t(GSR_STAGE_GATHER_BWD, st);
-        gsr_launch_reduce_instances(P, num_rendered, g.vals[depth_order_buffer_index()], g.offsets, g.splats, w.inst_grads,
-                                    w.inst_flag, sg, w.unit_first, w.unit_piece, st);
-        if (absgrad)
-            gsr_launch_absgrad_reduce(P, num_rendered, g.vals[depth_order_buffer_index()], g.offsets, w.inst_grads, w.inst_flag, sg, st);
+        gsr_launch_reduce_instances(P, num_rendered, f.order, f.offsets, f.splats, w.inst_grads, w.inst_flag, sg, w.unit_first, w.unit_piece, st);
+        if (absgrad) gsr_launch_absgrad_reduce(P, num_rendered, f, w.inst_grads, w.inst_flag, sg, st);
     }
     STAGE_CHECK("render backward reduce");
     HIP_OK(hipGetLastError());
@@ -1163,36 +1176,43 @@ int gsr_absgrad_from_records(const GsrRasterSettings* settings, int P, const flo
     return GSR_OK;
 }
 
+// The checks the read-only calls on a saved frame share (gsr_contribution_stats, gsr_pixel_probe, gsr_render_features, gsr_render_features_backward), in
+// the order their errors are reported: the settings, the counts, `own_error` -- what the call found wrong with its own arguments (NULL: nothing), which
+// needs none of the state -- and the state buffers.
+static int reader_args(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                       const void* image_buffer, const char* own_error, GsrCamDev& cam) {
+    int rc = make_cam(settings, 0, cam);
+    if (rc != GSR_OK) return rc;
+    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
+    if (own_error) return fail(GSR_ERR_INVALID_ARG, own_error);
+    if (P > 0 && num_rendered > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
+    return GSR_OK;
+}
+
 size_t gsr_contribution_scratch_bytes(int P, int64_t R) { (void)P; return gsr_carve_contrib(nullptr, R).bytes; }
 
 int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer,
                            const void* binning_buffer, const void* image_buffer, const float* pixel_weight, void* scratch,
                            const GsrContribOut* out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    GsrCamDev cam;
-    int rc = make_cam(settings, 0, cam);
-    if (rc != GSR_OK) return rc;
-    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
-    if (!out) return fail(GSR_ERR_INVALID_ARG, "out (GsrContribOut) is NULL");
-    if (out->accumulate != 0 && out->accumulate != 1) return fail(GSR_ERR_INVALID_ARG, "GsrContribOut.accumulate must be 0 or 1");
     const int64_t R = num_rendered;
-    if (R > 0 && !scratch) return fail(GSR_ERR_INVALID_ARG, "scratch is NULL (gsr_contribution_scratch_bytes)");
-    if (((uintptr_t)scratch) & 15) return fail(GSR_ERR_INVALID_ARG, "contribution scratch must be 16-byte aligned");
-    if (P > 0 && R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
-        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
+    const char* own = !out                                             ? "out (GsrContribOut) is NULL"
+                      : (out->accumulate != 0 && out->accumulate != 1) ? "GsrContribOut.accumulate must be 0 or 1"
+                      : (R > 0 && !scratch)                            ? "scratch is NULL (gsr_contribution_scratch_bytes)"
+                      : (((uintptr_t)scratch) & 15)                    ? "contribution scratch must be 16-byte aligned"
+                                                                       : nullptr;
+    GsrCamDev cam;
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
+    if (rc != GSR_OK) return rc;
     if (!out->accumulate && P > 0) {      // every row is written: Gaussians without instances keep these zeros
         if (out->weight_sum) HIP_OK(hipMemsetAsync(out->weight_sum, 0, (size_t)P * sizeof(float), st));
         if (out->weight_max) HIP_OK(hipMemsetAsync(out->weight_max, 0, (size_t)P * sizeof(float), st));
         if (out->pixel_count) HIP_OK(hipMemsetAsync(out->pixel_count, 0, (size_t)P * sizeof(int32_t), st));
     }
     if (P == 0 || R == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
-    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
-    const int list_buf = list_buffer_index(cam.gx * cam.gy);
-    gsr_launch_contribution_stats(cam, P, R, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, g.vals[depth_order_buffer_index()], g.offsets,
-                                  pixel_weight, gsr_carve_contrib((char*)scratch, R), out->weight_sum, out->weight_max, out->pixel_count,
-                                  out->accumulate, st);
+    gsr_launch_contribution_stats(cam, P, R, saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer), pixel_weight,
+                                  gsr_carve_contrib((char*)scratch, R), out->weight_sum, out->weight_max, out->pixel_count, out->accumulate, st);
     STAGE_CHECK("contribution statistics");
     HIP_OK(hipGetLastError());
     return GSR_OK;
@@ -1201,40 +1221,21 @@ int gsr_contribution_stats(const GsrRasterSettings* settings, int P, int32_t num
 int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
                     const void* image_buffer, const GsrPixelProbeOut* out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    const char* own = !out                                                 ? "out (GsrPixelProbeOut) is NULL"
+                      : !(out->threshold > 0.0f && out->threshold < 1.0f) ? "GsrPixelProbeOut.threshold must be inside (0, 1)"      // (a NaN fails both comparisons)
+                                                                           : nullptr;
     GsrCamDev cam;
-    int rc = make_cam(settings, 0, cam);
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
     if (rc != GSR_OK) return rc;
-    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
-    if (!out) return fail(GSR_ERR_INVALID_ARG, "out (GsrPixelProbeOut) is NULL");
-    if (!(out->threshold > 0.0f && out->threshold < 1.0f))      // (a NaN fails both comparisons)
-        return fail(GSR_ERR_INVALID_ARG, "GsrPixelProbeOut.threshold must be inside (0, 1)");
     const int64_t R = num_rendered;
-    if (P > 0 && R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
-        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
     if (P == 0 || R == 0) {      // no state to read: the defaults over the band
         gsr_launch_pixel_probe_defaults(cam, *out, st);
         HIP_OK(hipGetLastError());
         return GSR_OK;
     }
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
-    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
-    const int list_buf = list_buffer_index(cam.gx * cam.gy);
-    gsr_launch_pixel_probe(cam, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, *out, st);
+    gsr_launch_pixel_probe(cam, saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer), *out, st);
     STAGE_CHECK("pixel probe");
     HIP_OK(hipGetLastError());
-    return GSR_OK;
-}
-
-// the checks gsr_render_features and gsr_render_features_backward share (those of gsr_pixel_probe, plus the channel count)
-static int feature_args(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
-                        const void* image_buffer, int C, GsrCamDev& cam) {
-    int rc = make_cam(settings, 0, cam);
-    if (rc != GSR_OK) return rc;
-    if (P < 0 || num_rendered < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0 or num_rendered < 0");
-    if (C < 1 || C > GSR_MAX_FEATURE_CHANNELS) return fail(GSR_ERR_INVALID_ARG, "C (feature channels) must be inside [1, 1024]");
-    if (P > 0 && num_rendered > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
-        return fail(GSR_ERR_INVALID_ARG, "state buffers are NULL (run the forward with no_backward == 0)");
     return GSR_OK;
 }
 
@@ -1242,7 +1243,8 @@ int gsr_render_features(const GsrRasterSettings* settings, int P, int32_t num_re
                         const void* image_buffer, const float* features, int C, float* out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GsrCamDev cam;
-    int rc = feature_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, C, cam);
+    const char* own = (C < 1 || C > GSR_MAX_FEATURE_CHANNELS) ? "C (feature channels) must be inside [1, 1024]" : nullptr;
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
     if (rc != GSR_OK) return rc;
     if (P > 0 && (!features || !out)) return fail(GSR_ERR_INVALID_ARG, "features / out are NULL");
     const int64_t R = num_rendered;
@@ -1251,11 +1253,7 @@ int gsr_render_features(const GsrRasterSettings* settings, int P, int32_t num_re
         HIP_OK(hipGetLastError());
         return GSR_OK;
     }
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
-    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
-    const int list_buf = list_buffer_index(cam.gx * cam.gy);
-    gsr_launch_render_features(cam, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, features, C, out, st);
+    gsr_launch_render_features(cam, saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer), features, C, out, st);
     STAGE_CHECK("render features");
     HIP_OK(hipGetLastError());
     return GSR_OK;
@@ -1268,7 +1266,8 @@ int gsr_render_features_backward(const GsrRasterSettings* settings, int P, int32
                                  float* dL_dfeatures, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GsrCamDev cam;
-    int rc = feature_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, C, cam);
+    const char* own = (C < 1 || C > GSR_MAX_FEATURE_CHANNELS) ? "C (feature channels) must be inside [1, 1024]" : nullptr;
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
     if (rc != GSR_OK) return rc;
     if (P > 0 && (!dL_dout || !dL_dfeatures)) return fail(GSR_ERR_INVALID_ARG, "dL_dout / dL_dfeatures are NULL");
     const int64_t R = num_rendered;
@@ -1277,12 +1276,8 @@ int gsr_render_features_backward(const GsrRasterSettings* settings, int P, int32
     // every row is written: Gaussians without instances keep these zeros
     if (P > 0) HIP_OK(hipMemsetAsync(dL_dfeatures, 0, (size_t)P * (size_t)C * sizeof(float), st));
     if (P == 0 || R == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
-    GsrImage im = gsr_carve_image((char*)image_buffer, cam.W, cam.H);
-    const int list_buf = list_buffer_index(cam.gx * cam.gy);
-    gsr_launch_render_features_backward(cam, P, R, im.ranges, b.vals[list_buf], g.splats, im.n_contrib, g.vals[depth_order_buffer_index()], g.offsets,
-                                        dL_dout, C, gsr_carve_feature_grad((char*)scratch, R, C), dL_dfeatures, st);
+    gsr_launch_render_features_backward(cam, P, R, saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer), dL_dout, C,
+                                        gsr_carve_feature_grad((char*)scratch, R, C), dL_dfeatures, st);
     STAGE_CHECK("render features backward");
     HIP_OK(hipGetLastError());
     return GSR_OK;
@@ -1617,21 +1612,20 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 int gsr_forward_views(int P, int64_t R, int width, int height, const void* geom_buffer, const void* binning_buffer,
                       const void* image_buffer, GsrForwardViews* out) {
     if (!out || !geom_buffer || !image_buffer) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
-    GsrGeom g = gsr_carve_geom((char*)geom_buffer, P);
-    GsrImage im = gsr_carve_image((char*)image_buffer, width, height);
-    const int n_tiles = ((width + GSR_TILE - 1) / GSR_TILE) * ((height + GSR_TILE - 1) / GSR_TILE);
-    out->splats = (const float*)g.splats;
-    out->tiles_touched = g.tiles;
-    out->depth_order = g.vals[depth_order_buffer_index()];
-    out->point_list = nullptr;
-    if (binning_buffer && R > 0) {
-        GsrBinning b = gsr_carve_binning((char*)binning_buffer, R);
-        out->point_list = b.vals[list_buffer_index(n_tiles)];
-    }
-    out->ranges = (const uint32_t*)im.ranges;
-    out->final_T = im.final_T;
-    out->n_contrib = im.n_contrib;
-    out->tile_scan = g.offsets;
+    GsrCamDev cam{};      // (the view depends on the frame size alone)
+    cam.W = width;
+    cam.H = height;
+    cam.gx = (width + GSR_TILE - 1) / GSR_TILE;
+    cam.gy = (height + GSR_TILE - 1) / GSR_TILE;
+    const GsrSavedFrame f = saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer);
+    out->splats = (const float*)f.splats;
+    out->tiles_touched = f.tiles;
+    out->depth_order = f.order;
+    out->point_list = f.point_list;      // (NULL without a binning buffer or with R <= 0)
+    out->ranges = (const uint32_t*)f.ranges;
+    out->final_T = f.final_T;
+    out->n_contrib = f.n_contrib;
+    out->tile_scan = f.offsets;
     return GSR_OK;
 }
 

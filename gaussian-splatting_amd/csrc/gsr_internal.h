@@ -145,6 +145,34 @@ struct GsrImage {
 };
 GsrImage gsr_carve_image(char* base, int W, int H);
 
+// ---- what a finished tracking forward leaves in the three buffers for the calls that read it back (blend backward, contribution statistics, pixel
+// probe, feature render, gsr_forward_views): filled in ONE place, saved_frame() of gsr_api.cpp, which alone knows which ping-pong buffers hold the
+// sorted list and the depth order.  Host side only: launchers unpack it at the launch, no kernel takes it.
+struct GsrSavedFrame {
+    const uint2* ranges;            // [n_tiles]
+    const uint32_t* point_list;     // [R] Gaussian ids, tile by tile, front to back (NULL without a binning buffer or with R <= 0)
+    const float4* splats;           // [4P]
+    const float* final_T;           // [H*W]
+    const uint32_t* n_contrib;      // [H*W]
+    const uint32_t* block_steps;    // [n_tiles*4]
+    uint32_t* tile_order;           // [n_tiles*2] scratch of the backward's plan kernel (the one entry a reader writes)
+    const uint32_t* order;          // [P] the depth order
+    const uint32_t* offsets;        // [P] the tile scan: inclusive scan of tiles_touched in depth order
+    const uint32_t* tiles;          // [P] tiles_touched (shown by gsr_forward_views; no kernel reads it back)
+};
+
+// the band's pixel rows [row0, row1) are one contiguous range of every [H,W] array: `pixels` pixels from pixel `first` on
+struct GsrBandRows { int row0, row1; size_t first, pixels; };
+static inline GsrBandRows gsr_band_rows(const GsrCamDev& cam) {
+    const int t0 = cam.tile_y0 * GSR_TILE, t1 = cam.tile_y1 * GSR_TILE;
+    GsrBandRows b;
+    b.row0 = t0 < cam.H ? t0 : cam.H;
+    b.row1 = t1 < cam.H ? t1 : cam.H;
+    b.first = (size_t)b.row0 * cam.W;
+    b.pixels = b.row1 > b.row0 ? (size_t)(b.row1 - b.row0) * cam.W : 0;
+    return b;
+}
+
 // ---- kernel launchers (one per translation unit) ----
 // preprocess.hip  (compiled with -ffp-contract=off)
 // (the key-producing launchers return their grid size: the number of entries of fs.wg_range they fill)
@@ -283,6 +311,9 @@ void gsr_set_render_fwd_lds_pad(int bytes);      // render_fwd.hip (tuning optio
 // only in builds with -DGSR_AB_VARIANTS
 int gsr_render_backward_variant_available(int variant);
 int gsr_render_forward_variant_available(int variant);
+// Two launchers keep their pointer lists, this one and gsr_launch_reduce_instances: tests/simt/forward_harness.cpp drives both with vectors of its own
+// (no carved buffers) and, as the frozen harness of the kernel-source tests, is compiled unchanged against this header.  backward_blend unpacks its
+// GsrSavedFrame at these two calls; every other reader takes the view.
 void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
                                 const float4* splats, const float* final_T, const uint32_t* n_contrib,
                                 const uint32_t* block_steps, uint32_t* tile_order /*NULL: tiles in index order*/,
@@ -291,22 +322,19 @@ void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const
                                 int order_mode /*plan kernel: 1 tiles by the sum of their blocks, 2 tiles by their heaviest half, 3 half tiles (waves)*/,
                                 unsigned long long* counters, hipStream_t st);
 // the same with the optional per-pixel background / alpha-image gradient of gsr_backward_blend_composite (comp may be NULL: the plain call)
-void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
-                                          const float4* splats, const float* final_T, const uint32_t* n_contrib,
-                                          const uint32_t* block_steps, uint32_t* tile_order, const float* dL_dpix, const float* dL_dinvdepth,
-                                          float* splat_grads, float* inst_grads, uint32_t* inst_flag, int64_t R, int variant, int order_mode,
-                                          unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp);
+void gsr_launch_render_backward_composite(const GsrCamDev& cam, const GsrSavedFrame& f /*tile_order NULL: tiles in index order*/,
+                                          const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
+                                          uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters,
+                                          hipStream_t st, const GsrCompositeDev* comp);
 // the walk's ABS instantiations (gsr_backward_blend_abs): the same launch (plan kernel, flags, order) with words 10, 11 of every instance record
 // carrying the two absolute sums of absgrad.hip; default kernel only (no measurement-build variant)
-void gsr_launch_render_backward_abs(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
-                                    const float4* splats, const float* final_T, const uint32_t* n_contrib,
-                                    const uint32_t* block_steps, uint32_t* tile_order, const float* dL_dpix, const float* dL_dinvdepth,
+void gsr_launch_render_backward_abs(const GsrCamDev& cam, const GsrSavedFrame& f, const float* dL_dpix, const float* dL_dinvdepth,
                                     float* inst_grads, uint32_t* inst_flag, int64_t R, int order_mode,
                                     unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp);
 // absgrad.hip: words 10, 11 of splat_grads[g] <- the sum of words 10, 11 of g's flagged instance records (after gsr_launch_reduce_instances, same
 // stream); means2D_abs[P,3] = (0.5 W word 10, 0.5 H word 11, 0)
-void gsr_launch_absgrad_reduce(int P, int64_t R, const uint32_t* order, const uint32_t* offsets, const float* inst_grads, const uint32_t* inst_flag,
-                               float* splat_grads, hipStream_t st);
+void gsr_launch_absgrad_reduce(int P, int64_t R, const GsrSavedFrame& f, const float* inst_grads, const uint32_t* inst_flag, float* splat_grads,
+                               hipStream_t st);
 void gsr_launch_absgrad_from_records(int P, int W, int H, const float* splat_grads, float* means2D_abs, hipStream_t st);
 // background gradient (render_bwd.hip): dL_dbg_image[c][p] = T(p) * dL_dpix[c][p] and / or dL_dbg[c] = sum over p, with T = final_T inside the
 // band's pixel rows [row0, row1) (1 where final_T is NULL: no Gaussian at all) and 0 outside.  partials: gsr_bg_grad_blocks(W * H) * 3 doubles.
@@ -344,15 +372,13 @@ struct GsrContribScratch {
     size_t bytes;
 };
 GsrContribScratch gsr_carve_contrib(char* base, int64_t R);
-void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list, const float4* splats,
-                                   const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets, const float* pixel_weight /*[H*W] or NULL*/,
+void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* pixel_weight /*[H*W] or NULL*/,
                                    const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count /*each [P] or NULL*/,
                                    int accumulate, hipStream_t st);
 
 // probe.hip: per-pixel probe (gsr_pixel_probe).  No scratch.  The kernel writes every in-band, in-image pixel of the non-NULL arrays, the defaults
 // included; _defaults fills the band's rows without reading any state (the call with P == 0 or num_rendered == 0).
-void gsr_launch_pixel_probe(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
-                            const GsrPixelProbeOut& out, hipStream_t st);
+void gsr_launch_pixel_probe(const GsrCamDev& cam, const GsrSavedFrame& f, const GsrPixelProbeOut& out, hipStream_t st);
 void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOut& out, hipStream_t st);
 
 // features.hip: N-channel per-Gaussian features blended with a finished forward's weights (gsr_render_features / _backward).  The forward writes every
@@ -361,12 +387,10 @@ void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOu
 // tile, instance) holding the channel sums of one group, slot-major, and a flag word per instance; 64-bit offsets), reused by every channel group of a
 // call; rows of dL_dfeatures[P,C] of Gaussians without instances are not touched (the caller zeroes the array).
 GsrContribScratch gsr_carve_feature_grad(char* base, int64_t R, int C);
-void gsr_launch_render_features(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
-                                const float* features, int C, float* out, hipStream_t st);
+void gsr_launch_render_features(const GsrCamDev& cam, const GsrSavedFrame& f, const float* features, int C, float* out, hipStream_t st);
 void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out, hipStream_t st);
-void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const uint2* ranges, const uint32_t* point_list,
-                                         const float4* splats, const uint32_t* n_contrib, const uint32_t* order, const uint32_t* offsets,
-                                         const float* dL_dout, int C, const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st);
+void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* dL_dout, int C,
+                                         const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st);
 
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,

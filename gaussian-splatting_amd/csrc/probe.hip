@@ -130,17 +130,9 @@ probe_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, co
 
 }  // namespace
 
-// the band's rows are one contiguous range of every [H,W] array
-static void band_rows(const GsrCamDev& cam, size_t& first, size_t& pixels) {
-    const int t0 = cam.tile_y0 * GSR_TILE, t1 = cam.tile_y1 * GSR_TILE;
-    const int r0 = t0 < cam.H ? t0 : cam.H, r1 = t1 < cam.H ? t1 : cam.H;
-    first = (size_t)r0 * cam.W;
-    pixels = r1 > r0 ? (size_t)(r1 - r0) * cam.W : 0;
-}
-
 void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOut& out, hipStream_t st) {
-    size_t first, pixels;
-    band_rows(cam, first, pixels);
+    const GsrBandRows band = gsr_band_rows(cam);
+    const size_t first = band.first, pixels = band.pixels;
     if (pixels == 0) return;
     if (out.expected_depth) (void)hipMemsetAsync(out.expected_depth + first, 0, pixels * sizeof(float), st);
     if (out.median_depth) (void)hipMemsetAsync(out.median_depth + first, 0, pixels * sizeof(float), st);
@@ -150,10 +142,9 @@ void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOu
     if (out.count) (void)hipMemsetAsync(out.count + first, 0, pixels * sizeof(int32_t), st);
 }
 
-void gsr_launch_pixel_probe(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list, const float4* splats, const uint32_t* n_contrib,
-                            const GsrPixelProbeOut& out, hipStream_t st) {
+void gsr_launch_pixel_probe(const GsrCamDev& cam, const GsrSavedFrame& f, const GsrPixelProbeOut& out, hipStream_t st) {
     const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
     if (n_band_tiles <= 0) return;
     const int groups = (n_band_tiles + 7) / 8;
-    hipLaunchKernelGGL(probe_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, ranges, point_list, splats, n_contrib, out);
+    hipLaunchKernelGGL(probe_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib, out);
 }

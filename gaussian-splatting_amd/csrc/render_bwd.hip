@@ -812,7 +812,7 @@ int gsr_render_backward_variant_available(int variant) {
 }
 
 namespace {
-// body of the two launchers below (comp_in may be NULL: the plain call)
+// body of the three launchers below (comp_in may be NULL: the plain call)
 void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
                             const float4* splats, const float* final_T, const uint32_t* n_contrib,
                             const uint32_t* block_steps, uint32_t* tile_order,
@@ -875,24 +875,18 @@ void gsr_launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const
                            inst_grads, inst_flag, R, variant, order_mode, counters, st, nullptr);
 }
 
-void gsr_launch_render_backward_composite(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
-                                          const float4* splats, const float* final_T, const uint32_t* n_contrib,
-                                          const uint32_t* block_steps, uint32_t* tile_order,
-                                          const float* dL_dpix, const float* dL_dinvdepth, float* splat_grads, float* inst_grads,
-                                          uint32_t* inst_flag, int64_t R, int variant, int order_mode, unsigned long long* counters, hipStream_t st,
-                                          const GsrCompositeDev* comp) {
-    launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, splat_grads,
-                           inst_grads, inst_flag, R, variant, order_mode, counters, st, comp);
+void gsr_launch_render_backward_composite(const GsrCamDev& cam, const GsrSavedFrame& f, const float* dL_dpix, const float* dL_dinvdepth,
+                                          float* splat_grads, float* inst_grads, uint32_t* inst_flag, int64_t R, int variant, int order_mode,
+                                          unsigned long long* counters, hipStream_t st, const GsrCompositeDev* comp) {
+    launch_render_backward(cam, f.ranges, f.point_list, f.splats, f.final_T, f.n_contrib, f.block_steps, f.tile_order, dL_dpix, dL_dinvdepth,
+                           splat_grads, inst_grads, inst_flag, R, variant, order_mode, counters, st, comp);
 }
 
-void gsr_launch_render_backward_abs(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
-                                    const float4* splats, const float* final_T, const uint32_t* n_contrib,
-                                    const uint32_t* block_steps, uint32_t* tile_order,
-                                    const float* dL_dpix, const float* dL_dinvdepth, float* inst_grads,
+void gsr_launch_render_backward_abs(const GsrCamDev& cam, const GsrSavedFrame& f, const float* dL_dpix, const float* dL_dinvdepth, float* inst_grads,
                                     uint32_t* inst_flag, int64_t R, int order_mode, unsigned long long* counters, hipStream_t st,
                                     const GsrCompositeDev* comp) {
-    launch_render_backward(cam, ranges, point_list, splats, final_T, n_contrib, block_steps, tile_order, dL_dpix, dL_dinvdepth, nullptr,
-                           inst_grads, inst_flag, R, 0, order_mode, counters, st, comp, true);
+    launch_render_backward(cam, f.ranges, f.point_list, f.splats, f.final_T, f.n_contrib, f.block_steps, f.tile_order, dL_dpix, dL_dinvdepth,
+                           nullptr, inst_grads, inst_flag, R, 0, order_mode, counters, st, comp, true);
 }
 
 size_t gsr_reduce_units(int64_t R) { return (size_t)((R + RU - 1) / RU); }

@@ -1,8 +1,8 @@
 """Reference for the absolute screen-space gradients (include/gsr.h gsr_backward_blend_abs), built on the oracle without touching it, and the bars both
 test files hold the product to (tests/test_absgrad_cpu.py on the SIMT build, tests/test_gpu_absgrad.py on the MI355X).
 
-Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, power / alpha / keep / Tincl / Texcl / dead exactly as
-tests/contrib_reference.py (and oracle/torch_oracle.py:_blend_tile) compute them, evaluated in fp64.  For the contributors i of a pixel (keep & ~dead), with
+Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, the record of the shared walk
+(tests/blend_reference.py: power / alpha / keep / Tincl / Texcl / dead), evaluated in fp64.  For the contributors i of a pixel (keep & ~dead), with
 s_i = <c_i, dL/dC> + dL/dD / depth_i, w_i = alpha_i T_i, T_final the product of (1 - alpha) over the contributors, B the background and dL/dA the gradient of
 the alpha image 1 - T_final, the closed form of the blend's derivative with suffix sums:
     dL/dalpha_i = T_i s_i - (sum_{j>i} s_j w_j + T_final (<B, dL/dC> - dL/dA)) / (1 - alpha_i)
@@ -19,25 +19,16 @@ Bars (each measured distance is printed with helpers.parity_report under absgrad
 Test infrastructure."""
 import torch
 
-from helpers import O, parity_report
+from helpers import parity_report
+from blend_reference import mask_fragile, tiles  # noqa: F401  (mask_fragile: the tests reach it through this module)
 
-TILE = 16
 BAR = 1e-5
-
-
-def mask_fragile(w, aux):
-    """A per-pixel loss weight [..., H, W] with the fragile pixels zeroed."""
-    w = w.clone()
-    w[..., aux["fragile"]] = 0.0
-    return w
 
 
 def reference(aux, s, dL_dC, dL_dD=None, dL_dA=None, bg=None, dtype=torch.float64):
     """dL_dC [3,H,W], dL_dD [H,W] / [1,H,W] or None, dL_dA (gradient of the alpha image) likewise, bg [3] or [3,H,W] (None: zeros)
     -> dict(abs [P,2], signed [P,2] in `dtype`, units of means2D.grad; pairs = number of contributing (pixel, Gaussian) pairs)."""
     W, H = int(s.image_width), int(s.image_height)
-    gx, _ = aux["grid"]
-    y0, y1 = aux["band"]
     P = aux["means2D"].shape[0]
     gC = dL_dC.detach().reshape(3, H, W).to(dtype)
     gD = torch.zeros(H, W, dtype=dtype) if dL_dD is None else dL_dD.detach().reshape(H, W).to(dtype)
@@ -45,46 +36,24 @@ def reference(aux, s, dL_dC, dL_dD=None, dL_dA=None, bg=None, dtype=torch.float6
     bg = torch.zeros(3) if bg is None else bg.detach()
     Bimg = (bg.reshape(3, 1, 1).expand(3, H, W) if bg.dim() == 1 else bg).to(dtype)
     bgdot = (Bimg * gC).sum(0) - gA                                  # <B, dL/dC> - dL/dA
-    xy_all, conic_all, op_all, rgb_all = (aux[k].detach().to(dtype) for k in ("means2D", "conic", "opacity", "rgb"))
-    op_all = op_all.reshape(-1)
+    rgb_all = aux["rgb"].detach().to(dtype)
     invd_all = 1.0 / aux["depths"].detach().to(dtype)
     ab, sg = torch.zeros(P, 2, dtype=dtype), torch.zeros(P, 2, dtype=dtype)
     pairs = 0
-    for t in range(y0 * gx, y1 * gx):
-        tyi, txi = divmod(int(t), gx)
-        x0, yy0 = txi * TILE, tyi * TILE
-        x1, yy1 = min(x0 + TILE, W), min(yy0 + TILE, H)
-        a, b = int(aux["ranges"][t, 0]), int(aux["ranges"][t, 1])
-        if b <= a:
-            continue
-        ids = aux["point_list"][a:b].long()
-        ys, xs = torch.meshgrid(torch.arange(yy0, yy1), torch.arange(x0, x1), indexing="ij")
-        px, py = xs.reshape(-1).to(dtype), ys.reshape(-1).to(dtype)
-        n = px.shape[0]
-        xy, conic, opac = xy_all[ids], conic_all[ids], op_all[ids]
-        dx = xy[None, :, 0] - px[:, None]
-        dy = xy[None, :, 1] - py[:, None]
-        A, B, Cc = conic[None, :, 0], conic[None, :, 1], conic[None, :, 2]
-        power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
-        a_raw = opac[None, :] * torch.exp(power)
-        alpha = torch.clamp(a_raw, max=O.ALPHA_MAX)
-        keep = (power <= 0) & (alpha >= O.ALPHA_MIN)
-        alpha_eff = torch.where(keep, alpha, torch.zeros_like(alpha))
-        Tincl = torch.cumprod(1.0 - alpha_eff, dim=1)
-        Texcl = torch.cat([torch.ones(n, 1, dtype=dtype), Tincl[:, :-1]], dim=1)
-        term = keep & (Tincl < O.T_EPS)
-        dead = torch.cumsum(term.to(torch.int32), dim=1) > 0
-        contrib = keep & ~dead
+    for t in tiles(aux, s, dtype):
+        yy0, yy1, x0, x1 = t.window
+        ids, dx, dy, A, B, Cc, Texcl, dead = t.ids, t.dx, t.dy, t.A, t.B, t.Cc, t.Texcl, t.dead
+        contrib = t.keep & ~dead
         first_dead = torch.argmax(dead.to(torch.int8), dim=1)
-        T_final = torch.where(dead[:, -1], torch.gather(Texcl, 1, first_dead[:, None])[:, 0], Tincl[:, -1])
+        T_final = torch.where(dead[:, -1], torch.gather(Texcl, 1, first_dead[:, None])[:, 0], t.Tincl[:, -1])
         gc = gC[:, yy0:yy1, x0:x1].reshape(3, -1)                       # [3, n]
         s_i = (rgb_all[ids] @ gc).T + invd_all[ids][None, :] * gD[yy0:yy1, x0:x1].reshape(-1)[:, None]      # [n, N]
-        w = torch.where(contrib, alpha_eff * Texcl, torch.zeros_like(alpha))
+        w = torch.where(contrib, t.alpha_eff * Texcl, torch.zeros_like(t.alpha))
         sw = s_i * w
         suffix = torch.flip(torch.cumsum(torch.flip(sw, dims=[1]), dim=1), dims=[1]) - sw                  # sum_{j>i} s_j w_j
         tail = (T_final * bgdot[yy0:yy1, x0:x1].reshape(-1))[:, None]
-        dL_dalpha = Texcl * s_i - (suffix + tail) / (1.0 - alpha_eff)
-        m = torch.where(contrib, a_raw * dL_dalpha, torch.zeros_like(alpha))
+        dL_dalpha = Texcl * s_i - (suffix + tail) / (1.0 - t.alpha_eff)
+        m = torch.where(contrib, t.a_raw * dL_dalpha, torch.zeros_like(t.alpha))
         ex = m * (A * dx + B * dy)
         ey = m * (Cc * dy + B * dx)
         ab.index_add_(0, ids, torch.stack([ex.abs().sum(0), ey.abs().sum(0)], dim=1))

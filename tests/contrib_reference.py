@@ -1,8 +1,8 @@
 """Reference for the per-Gaussian blend-weight statistics (include/gsr.h gsr_contribution_stats), built on the oracle without touching it, and
 the bars both test files hold the product to (tests/test_contrib_cpu.py on the SIMT build, tests/test_gpu_contrib.py on the MI355X).
 
-Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, power / alpha / keep / Tincl / Texcl / dead exactly as
-oracle/torch_oracle.py:_blend_tile computes them, evaluated in fp64; contrib = keep & ~dead & (E != 0), w = alpha * Texcl * E, scattered onto the
+Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, the record of the shared walk
+(tests/blend_reference.py: power / alpha / keep / Tincl / Texcl / dead), evaluated in fp64; contrib = keep & ~dead & (E != 0), w = alpha * Texcl * E, scattered onto the
 Gaussians (index_add_ of the sums and counts, amax onto a zero vector).  Pixels of aux["fragile"] -- where a hard threshold sits inside rounding
 noise, the project's accepted notion -- get E = 0 in the tests' inputs (mask_fragile), for the product and the reference alike.
 
@@ -16,9 +16,8 @@ Bars (each measured distance is printed with helpers.parity_report under contrib
 Test infrastructure."""
 import torch
 
-from helpers import O, parity_report
-
-TILE = 16
+from helpers import parity_report
+from blend_reference import mask_fragile, near_threshold, tiles  # noqa: F401  (mask_fragile: the tests reach it through this module)
 
 
 def raise_opacity(opacities, logits=3.0):
@@ -26,62 +25,28 @@ def raise_opacity(opacities, logits=3.0):
     return torch.sigmoid(torch.logit(opacities.double()) + logits).float()
 
 
-def mask_fragile(E, aux):
-    E = E.clone()
-    E[aux["fragile"]] = 0.0
-    return E
-
-
 def reference(aux, s, E=None, dtype=torch.float64):
     """-> dict(weight_sum[P], weight_max[P] in `dtype`, pixel_count[P] int64, near[P] bool: a pair of the Gaussian that the sequential loop evaluates at a
     pixel with E != 0 has alpha within 1e-4 relative of 1/255 or T (after it) within 1e-4 relative of 1e-4, terminated [H,W] bool, longest list)."""
     W, H = int(s.image_width), int(s.image_height)
-    gx, _ = aux["grid"]
-    y0, y1 = aux["band"]
     P = aux["means2D"].shape[0]
     E = torch.ones(H, W, dtype=dtype) if E is None else E.detach().reshape(H, W).to(dtype)
-    xy_all, conic_all, op_all = (aux[k].detach().to(dtype) for k in ("means2D", "conic", "opacity"))
-    op_all = op_all.reshape(-1)
     wsum, wmax = torch.zeros(P, dtype=dtype), torch.zeros(P, dtype=dtype)
     count, near = torch.zeros(P, dtype=torch.int64), torch.zeros(P, dtype=torch.int64)
     terminated = torch.zeros(H, W, dtype=torch.bool)
     longest = 0
-    for t in range(y0 * gx, y1 * gx):
-        tyi, txi = divmod(int(t), gx)
-        x0, yy0 = txi * TILE, tyi * TILE
-        x1, yy1 = min(x0 + TILE, W), min(yy0 + TILE, H)
-        a, b = int(aux["ranges"][t, 0]), int(aux["ranges"][t, 1])
-        if b <= a:
-            continue
-        longest = max(longest, b - a)
-        ids = aux["point_list"][a:b].long()
-        ys, xs = torch.meshgrid(torch.arange(yy0, yy1), torch.arange(x0, x1), indexing="ij")
-        px, py = xs.reshape(-1).to(dtype), ys.reshape(-1).to(dtype)
-        n = px.shape[0]
-        xy, conic, opac = xy_all[ids], conic_all[ids], op_all[ids]
-        dx = xy[None, :, 0] - px[:, None]
-        dy = xy[None, :, 1] - py[:, None]
-        A, B, Cc = conic[None, :, 0], conic[None, :, 1], conic[None, :, 2]
-        power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
-        alpha = torch.clamp(opac[None, :] * torch.exp(power), max=O.ALPHA_MAX)
-        keep = (power <= 0) & (alpha >= O.ALPHA_MIN)
-        alpha_eff = torch.where(keep, alpha, torch.zeros_like(alpha))
-        Tincl = torch.cumprod(1.0 - alpha_eff, dim=1)
-        Texcl = torch.cat([torch.ones(n, 1, dtype=dtype), Tincl[:, :-1]], dim=1)
-        term = keep & (Tincl < O.T_EPS)
-        dead = torch.cumsum(term.to(torch.int32), dim=1) > 0
+    for t in tiles(aux, s, dtype):
+        yy0, yy1, x0, x1 = t.window
+        longest = max(longest, t.ids.shape[0])
         e = E[yy0:yy1, x0:x1].reshape(-1)
         on = (e != 0)[:, None]
-        contrib = keep & ~dead & on
-        w = torch.where(contrib, alpha_eff * Texcl * e[:, None], torch.zeros_like(alpha))
-        wsum.index_add_(0, ids, w.sum(0))
-        count.index_add_(0, ids, contrib.sum(0))
-        wmax.scatter_reduce_(0, ids, w.max(0).values, reduce="amax", include_self=True)
-        live = (~dead | term) & on
-        near_a = (alpha - O.ALPHA_MIN).abs() < 1e-4 * O.ALPHA_MIN
-        near_t = keep & ((Tincl - O.T_EPS).abs() < 1e-4 * O.T_EPS)
-        near.index_add_(0, ids, ((near_a | near_t) & live).sum(0))
-        terminated[yy0:yy1, x0:x1] = dead[:, -1].reshape(yy1 - yy0, x1 - x0)
+        contrib = t.keep & ~t.dead & on
+        w = torch.where(contrib, t.alpha_eff * t.Texcl * e[:, None], torch.zeros_like(t.alpha))
+        wsum.index_add_(0, t.ids, w.sum(0))
+        count.index_add_(0, t.ids, contrib.sum(0))
+        wmax.scatter_reduce_(0, t.ids, w.max(0).values, reduce="amax", include_self=True)
+        near.index_add_(0, t.ids, (near_threshold(t) & on).sum(0))
+        terminated[yy0:yy1, x0:x1] = t.dead[:, -1].reshape(yy1 - yy0, x1 - x0)
     return dict(weight_sum=wsum, weight_max=wmax, pixel_count=count, near=near > 0, terminated=terminated, longest=longest)
 
 

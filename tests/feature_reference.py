@@ -1,14 +1,14 @@
 """Reference for the N-channel feature render (include/gsr.h gsr_render_features / gsr_render_features_backward), built on the oracle without touching it,
 and the bars both test files hold the product to (tests/test_features_cpu.py on the SIMT build, tests/test_gpu_features.py on the MI355X).
 
-Forward: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, power / alpha / keep / Tincl / Texcl / dead exactly as
-tests/contrib_reference.py (and oracle/torch_oracle.py:_blend_tile) compute them, evaluated in fp64; w = alpha_eff * Texcl under keep & ~dead, and
+Forward: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, the record of the shared walk
+(tests/blend_reference.py: power / alpha / keep / Tincl / Texcl / dead), evaluated in fp64; w = alpha_eff * Texcl under keep & ~dead, and
 F[c] = sum w f[:,c].  Pixels outside the band are 0.
 Gradient: dL/df[:,c] = contrib_reference.reference(aux, s, E=G_c)["weight_sum"], channel by channel: the same sum with the upstream gradient of the
 channel as the pixel weight (gradient_per_channel); gradient() computes those sums for all channels from one evaluation of a tile's weights.
 
 Pixels of aux["fragile"] -- where a hard threshold sits inside rounding noise, the project's accepted notion -- are excluded from image comparisons and get
-a zero upstream gradient in gradient tests (contrib_reference.mask_fragile), for the product and the reference alike.
+a zero upstream gradient in gradient tests (blend_reference.mask_fragile), for the product and the reference alike.
 
 Bars, both the project's own (each measured distance is printed with helpers.parity_report under features_*):
   image      per channel within 1e-5 * max |f| absolute: a sum of blend weights (<= 1 in total) times values of at most max |f|, the image bar scaled;
@@ -17,44 +17,14 @@ Bars, both the project's own (each measured distance is printed with helpers.par
 Test infrastructure."""
 import torch
 
-from helpers import O, parity_report
+from helpers import parity_report
+from blend_reference import mask_fragile, tiles  # noqa: F401  (mask_fragile: the tests reach it through this module)
 import contrib_reference as CR
 
-TILE = 16
-mask_fragile = CR.mask_fragile
 
-
-def _tiles(aux, s, dtype):
-    """Per tile of the band with a non-empty range: (ids, pixel window, w[pixels, entries]) with w = alpha_eff * Texcl under keep & ~dead."""
-    W, H = int(s.image_width), int(s.image_height)
-    gx, _ = aux["grid"]
-    y0, y1 = aux["band"]
-    xy_all, conic_all, op_all = (aux[k].detach().to(dtype) for k in ("means2D", "conic", "opacity"))
-    op_all = op_all.reshape(-1)
-    for t in range(y0 * gx, y1 * gx):
-        tyi, txi = divmod(int(t), gx)
-        x0, yy0 = txi * TILE, tyi * TILE
-        x1, yy1 = min(x0 + TILE, W), min(yy0 + TILE, H)
-        a, b = int(aux["ranges"][t, 0]), int(aux["ranges"][t, 1])
-        if b <= a:
-            continue
-        ids = aux["point_list"][a:b].long()
-        ys, xs = torch.meshgrid(torch.arange(yy0, yy1), torch.arange(x0, x1), indexing="ij")
-        px, py = xs.reshape(-1).to(dtype), ys.reshape(-1).to(dtype)
-        n = px.shape[0]
-        xy, conic, opac = xy_all[ids], conic_all[ids], op_all[ids]
-        dx = xy[None, :, 0] - px[:, None]
-        dy = xy[None, :, 1] - py[:, None]
-        A, B, Cc = conic[None, :, 0], conic[None, :, 1], conic[None, :, 2]
-        power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
-        alpha = torch.clamp(opac[None, :] * torch.exp(power), max=O.ALPHA_MAX)
-        keep = (power <= 0) & (alpha >= O.ALPHA_MIN)
-        alpha_eff = torch.where(keep, alpha, torch.zeros_like(alpha))
-        Tincl = torch.cumprod(1.0 - alpha_eff, dim=1)
-        Texcl = torch.cat([torch.ones(n, 1, dtype=dtype), Tincl[:, :-1]], dim=1)
-        term = keep & (Tincl < O.T_EPS)
-        dead = torch.cumsum(term.to(torch.int32), dim=1) > 0
-        yield ids, (yy0, yy1, x0, x1), torch.where(keep & ~dead, alpha_eff * Texcl, torch.zeros_like(alpha))
+def _weights(t):
+    """w[pixels, entries] of a tile's record: alpha_eff * Texcl under keep & ~dead."""
+    return torch.where(t.keep & ~t.dead, t.alpha_eff * t.Texcl, torch.zeros_like(t.alpha))
 
 
 def forward(aux, s, features, dtype=torch.float64):
@@ -62,8 +32,9 @@ def forward(aux, s, features, dtype=torch.float64):
     f_all = features.detach().to(dtype)
     C = f_all.shape[1]
     F = torch.zeros(C, int(s.image_height), int(s.image_width), dtype=dtype)
-    for ids, (yy0, yy1, x0, x1), w in _tiles(aux, s, dtype):
-        F[:, yy0:yy1, x0:x1] = (w @ f_all[ids]).T.reshape(C, yy1 - yy0, x1 - x0)
+    for t in tiles(aux, s, dtype):
+        yy0, yy1, x0, x1 = t.window
+        F[:, yy0:yy1, x0:x1] = (_weights(t) @ f_all[t.ids]).T.reshape(C, yy1 - yy0, x1 - x0)
     return F
 
 
@@ -78,8 +49,9 @@ def gradient(aux, s, G, dtype=torch.float64):
     G = G.detach().to(dtype)
     C = G.shape[0]
     out = torch.zeros(aux["means2D"].shape[0], C, dtype=dtype)
-    for ids, (yy0, yy1, x0, x1), w in _tiles(aux, s, dtype):
-        out.index_add_(0, ids, w.T @ G[:, yy0:yy1, x0:x1].reshape(C, -1).T)
+    for t in tiles(aux, s, dtype):
+        yy0, yy1, x0, x1 = t.window
+        out.index_add_(0, t.ids, _weights(t).T @ G[:, yy0:yy1, x0:x1].reshape(C, -1).T)
     return out
 
 

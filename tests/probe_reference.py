@@ -1,15 +1,15 @@
 """Reference for the per-pixel probe (include/gsr.h gsr_pixel_probe), built on the oracle without touching it, and the bars both test files hold the
 product to (tests/test_probe_cpu.py on the SIMT build, tests/test_gpu_probe.py on the MI355X).
 
-Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, power / alpha / keep / Tincl / Texcl / dead exactly as
-tests/contrib_reference.py (and oracle/torch_oracle.py:_blend_tile) compute them, evaluated in fp64; contrib = keep & ~dead, w = alpha * Texcl, T' = Tincl,
+Reference: from `aux` of O.rasterize(..., want_fragile=True, return_aux=True), per tile of the band, the record of the shared walk
+(tests/blend_reference.py: power / alpha / keep / Tincl / Texcl / dead), evaluated in fp64; contrib = keep & ~dead, w = alpha * Texcl, T' = Tincl,
 z = aux["depths"], g = aux["point_list"].  Per pixel: count = #contrib, expected_depth = sum w z, median = the first contributor with T' < threshold,
 top = the contributor with the largest w.  Pixels without a contributor, and pixels outside the band, hold the defaults (0, 0, -1, -1, 0, 0).
 
 Near flags, per pixel -- where a discrete output may legitimately differ between fp32 and fp64:
   near_median  some contributor has T' within 1e-4 relative of the threshold;
   near_top     the two largest weights of the pixel's contributors differ by less than 1e-5;
-  near_count   the flag of contrib_reference: an evaluated pair has alpha within 1e-4 relative of 1/255 or T' within 1e-4 relative of 1e-4.  An entry that
+  near_count   blend_reference.near_threshold: an evaluated pair has alpha within 1e-4 relative of 1/255 or T' within 1e-4 relative of 1e-4.  An entry that
                flips there also scales every later T of the pixel by (1 - alpha), so it explains a median or top mismatch of that pixel as well.
 
 Bars (each measured distance is printed with helpers.parity_report under probe_*), on pixels outside aux["fragile"]:
@@ -22,55 +22,32 @@ Bars (each measured distance is printed with helpers.parity_report under probe_*
 Test infrastructure."""
 import torch
 
-from helpers import O, parity_report
-
-TILE = 16
+from helpers import parity_report
+from blend_reference import near_threshold, tiles
 
 
 def reference(aux, s, threshold=0.5, dtype=torch.float64):
     """-> dict of [H,W] tensors: expected_depth, top_weight (`dtype`), median_id, top_id, count (int64), near_median, near_top, near_count, terminated
     (bool), and `longest` (the longest list)."""
     W, H = int(s.image_width), int(s.image_height)
-    gx, _ = aux["grid"]
-    y0, y1 = aux["band"]
-    xy_all, conic_all, op_all, z_all = (aux[k].detach().to(dtype) for k in ("means2D", "conic", "opacity", "depths"))
-    op_all = op_all.reshape(-1)
+    z_all = aux["depths"].detach().to(dtype)
     e_depth, top_w = torch.zeros(H, W, dtype=dtype), torch.zeros(H, W, dtype=dtype)
     med_id, top_id = torch.full((H, W), -1, dtype=torch.int64), torch.full((H, W), -1, dtype=torch.int64)
     count = torch.zeros(H, W, dtype=torch.int64)
     near_m, near_t, near_c, terminated = (torch.zeros(H, W, dtype=torch.bool) for _ in range(4))
     longest = 0
-    for t in range(y0 * gx, y1 * gx):
-        tyi, txi = divmod(int(t), gx)
-        x0, yy0 = txi * TILE, tyi * TILE
-        x1, yy1 = min(x0 + TILE, W), min(yy0 + TILE, H)
-        a, b = int(aux["ranges"][t, 0]), int(aux["ranges"][t, 1])
-        if b <= a:
-            continue
-        longest = max(longest, b - a)
-        ids = aux["point_list"][a:b].long()
-        ys, xs = torch.meshgrid(torch.arange(yy0, yy1), torch.arange(x0, x1), indexing="ij")
-        px, py = xs.reshape(-1).to(dtype), ys.reshape(-1).to(dtype)
-        n, hh, ww = px.shape[0], yy1 - yy0, x1 - x0
-        xy, conic, opac, z = xy_all[ids], conic_all[ids], op_all[ids], z_all[ids]
-        dx = xy[None, :, 0] - px[:, None]
-        dy = xy[None, :, 1] - py[:, None]
-        A, B, Cc = conic[None, :, 0], conic[None, :, 1], conic[None, :, 2]
-        power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
-        alpha = torch.clamp(opac[None, :] * torch.exp(power), max=O.ALPHA_MAX)
-        keep = (power <= 0) & (alpha >= O.ALPHA_MIN)
-        alpha_eff = torch.where(keep, alpha, torch.zeros_like(alpha))
-        Tincl = torch.cumprod(1.0 - alpha_eff, dim=1)
-        Texcl = torch.cat([torch.ones(n, 1, dtype=dtype), Tincl[:, :-1]], dim=1)
-        term = keep & (Tincl < O.T_EPS)
-        dead = torch.cumsum(term.to(torch.int32), dim=1) > 0
-        contrib = keep & ~dead
-        w = torch.where(contrib, alpha_eff * Texcl, torch.zeros_like(alpha))
+    for t in tiles(aux, s, dtype):
+        yy0, yy1, x0, x1 = t.window
+        ids, n, hh, ww = t.ids, t.n, yy1 - yy0, x1 - x0
+        longest = max(longest, ids.shape[0])
+        z = z_all[ids]
+        contrib = t.keep & ~t.dead
+        w = torch.where(contrib, t.alpha_eff * t.Texcl, torch.zeros_like(t.alpha))
         has = contrib.any(1)
         put = lambda dst, v: dst[yy0:yy1, x0:x1].copy_(v.reshape(hh, ww))      # noqa: E731
         put(count, contrib.sum(1))
         put(e_depth, (w * z[None, :]).sum(1))
-        below = contrib & (Tincl < threshold)
+        below = contrib & (t.Tincl < threshold)
         first = below.to(torch.int8).argmax(1)      # (the first maximum: the first True)
         put(med_id, torch.where(below.any(1), ids[first], torch.full_like(first, -1)))
         ranked = torch.where(contrib, w, torch.full_like(w, -1.0))
@@ -80,12 +57,9 @@ def reference(aux, s, threshold=0.5, dtype=torch.float64):
         put(top_id, torch.where(has, ids[best.indices[:, 0]], torch.full_like(first, -1)))
         if k == 2:
             put(near_t, (best.values[:, 1] > 0) & (best.values[:, 0] - best.values[:, 1] < 1e-5))
-        put(near_m, (contrib & ((Tincl - threshold).abs() < 1e-4 * threshold)).any(1))
-        live = ~dead | term
-        near_a = (alpha - O.ALPHA_MIN).abs() < 1e-4 * O.ALPHA_MIN
-        near_e = keep & ((Tincl - O.T_EPS).abs() < 1e-4 * O.T_EPS)
-        put(near_c, ((near_a | near_e) & live).any(1))
-        put(terminated, dead[:, -1])
+        put(near_m, (contrib & ((t.Tincl - threshold).abs() < 1e-4 * threshold)).any(1))
+        put(near_c, near_threshold(t).any(1))
+        put(terminated, t.dead[:, -1])
     return dict(expected_depth=e_depth, top_weight=top_w, median_id=med_id, top_id=top_id, count=count, near_median=near_m, near_top=near_t,
                 near_count=near_c, terminated=terminated, longest=longest)
 
