@@ -412,6 +412,22 @@ int gsr_set_option(const char* name, int value) {
         return GSR_OK;
     }
     if (!strcmp(name, "preprocess_grid_cap")) { gsr_set_preprocess_grid_cap(value); return GSR_OK; }
+    if (!strcmp(name, "preprocess_generic")) {
+        if (value != 0 && value != 1) return fail(GSR_ERR_INVALID_ARG, "preprocess_generic must be 0 (the call form picks the forward instantiation) or 1 (always the generic one)");
+        gsr_set_preprocess_generic(value);
+        return GSR_OK;
+    }
+    if (!strcmp(name, "preprocess_hot_grid")) {
+        if (value < 0 || value > GSR_FRAME_MAX_GROUPS) return fail(GSR_ERR_INVALID_ARG, "preprocess_hot_grid must be 0 (from the occupancy) or 1..2047 workgroups");
+        gsr_set_preprocess_hot_grid(value);
+        return GSR_OK;
+    }
+    if (!strcmp(name, "debug_last_preprocess_path")) {      // test hook, changes nothing: succeeds iff the most recent forward took this path
+        if (value != 1 && value != 2) return fail(GSR_ERR_INVALID_ARG, "debug_last_preprocess_path: 1 (generic) or 2 (hot)");
+        if (gsr_preprocess_last_path() != value)
+            return fail(GSR_ERR_INVALID_ARG, gsr_preprocess_last_path() == 2 ? "the last forward preprocess ran a hot instantiation" : gsr_preprocess_last_path() == 1 ? "the last forward preprocess ran the generic instantiation" : "no forward preprocess has run yet");
+        return GSR_OK;
+    }
     if (!strcmp(name, "ssim_variant")) {
         if (value != 0 && value != 1) return fail(GSR_ERR_INVALID_ARG, "ssim_variant must be 0 (marching waves) or 1 (LDS tiles)");
         gsr_set_ssim_variant(value);

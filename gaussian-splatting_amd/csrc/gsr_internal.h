@@ -212,6 +212,9 @@ void gsr_launch_preprocess_backward_sh_adam(const GsrCamDev& cam, int P, const f
                                             float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dscales,
                                             float* dL_drotations, const GsrShAdamDev& adam, hipStream_t st);
 void gsr_set_preprocess_grid_cap(int cap);      // tuning knob (option preprocess_grid_cap)
+void gsr_set_preprocess_generic(int on);        // A/B switch (option preprocess_generic): 1 = the forward always runs its generic instantiation
+void gsr_set_preprocess_hot_grid(int groups);   // tuning knob (option preprocess_hot_grid): workgroups of the hot forward instantiations, 0 = from the occupancy
+int gsr_preprocess_last_path(void);             // the most recent gsr_launch_preprocess: 1 = generic instantiation, 2 = hot (0: none yet)
 void gsr_launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);
 
 // sort.hip: LSD radix sort of (u32 key, u32 value) pairs on bits [0, nbits); returns the index (0/1) of the

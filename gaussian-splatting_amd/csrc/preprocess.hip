@@ -15,12 +15,14 @@
 #include "gsr_internal.h"
 #include "gsr_adam_math.h"
 #include "gsr_frame.h"
+#include <atomic>
 
 namespace {
 
 // occupancy attributes of the two per-Gaussian kernels (tuning builds: GSR_EXTRA_FLAGS=-DGSR_PRE_OCC_FWD=__attribute__((amdgpu_waves_per_eu(3,3)))).
-// Default: none -- the kernels take 177-212 VGPRs = two waves per SIMD.  Three waves per SIMD (168 VGPRs; three 53 KB workgroups also fill
-// the CU's LDS exactly) cost 25-49 spilled registers in round 2 (measured slower) and 8-36 with the round-4 kernels.
+// Default: none -- the backward and the forward's generic instantiation take 177-212 VGPRs = two waves per SIMD (the forward's hot
+// instantiations, GsrPreHot below, take 145-163 = three).  Forcing three waves per SIMD (168 VGPRs; three 53 KB workgroups also fill
+// the CU's LDS exactly) on the unspecialised code cost 25-49 spilled registers in round 2 (measured slower) and 8-36 with the round-4 kernels.
 #ifndef GSR_PRE_OCC_FWD
 #define GSR_PRE_OCC_FWD
 #endif
@@ -101,7 +103,9 @@ __device__ __forceinline__ void wave_issue_sh16(const float* __restrict__ shs, i
     for (int it = 0; it < 12; ++it) {
         const int idx = it * 64 + lane;
         const int g = idx / 12;
-        reg[it] = (i0 + g < P) ? src[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        // a piece of a row past P reads the block's first 16 bytes instead (always valid, always cached) and lands in a tile row nobody reads:
+        // selecting zeros here cost a branch around every load plus 48 register clears per trip for the last block's sake
+        reg[it] = src[(i0 + g < P) ? idx : 0];
     }
 }
 __device__ __forceinline__ void wave_commit_sh16(const float4 (&reg)[12], uint64_t rows, int lane, float* tile) {
@@ -199,9 +203,26 @@ __device__ __forceinline__ void wave_store_sh_split_dense(float* __restrict__ d_
     }
     __builtin_amdgcn_wave_barrier();
 }
+// The call form of the forward kernel, as far as the launcher can fix it at compile time (gsr_launch_preprocess).  A field that is
+// PRE_RT is tested at run time on every trip of the grid-stride loop, as all of them were before round 7; a fixed field folds its
+// branches away -- with them the registers that kept the other side's pointers, zero records and camera fields alive (the fused-SH
+// generic instantiation: 201 VGPRs, 97 SGPRs parked in VGPR lanes; the hot one: tools/isa_audit.py preprocess_forward).
+// The arithmetic is one body: no expression differs between the instantiations, every output is the same bits.
+constexpr int PRE_RT = -1;
+constexpr int PRE_GEO_SCALE_ROT = 0, PRE_GEO_COV3D = 1;                  // geometry source: scales + rotations | cov3D_precomp
+constexpr int PRE_COL_SH16 = 0, PRE_COL_PRECOMP = 1, PRE_COL_SH = 2;     // colour source: staged SH (M == 16) | colors_precomp | SH read per lane
+template <int GEO, int COL, int SPEC, int CLAMP>
+struct GsrPreForm {
+    static constexpr int geo = GEO, col = COL, spec = SPEC /* 1: SH block requested up front */, clamp = CLAMP /* 1: clamped_out written */;
+};
+typedef GsrPreForm<PRE_RT, PRE_RT, PRE_RT, PRE_RT> GsrPreGeneric;
+// what the benchmark, the training legs and every single-GPU caller run: scales + rotations, a 16-coefficient SH tensor (fused or
+// dc / rest), a band of a quarter of the frame or more, no clamp output
+typedef GsrPreForm<PRE_GEO_SCALE_ROT, PRE_COL_SH16, 1, 0> GsrPreHot;
+
 // SPLIT = the separate dc / rest form (always staged: the C ABI accepts it only for M == 16 and 16-byte aligned pointers)
 // fs: frame statistics (gsr_frame.h) -- the kernel's last workgroup publishes R and the depth-key range
-template <bool SPLIT>
+template <bool SPLIT, class FORM>
 __global__ void __launch_bounds__(256) GSR_PRE_OCC_FWD
 preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, const float* __restrict__ shs,
                       const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -216,15 +237,21 @@ preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float* tile = s_sh[wv];
     const float* dc = SPLIT ? camd.sh_dc : nullptr;          // split form: `shs` holds coefficients 1..15
-    const bool staged_sh = shs != nullptr && cam.M == 16;
+    const bool has_cov = FORM::geo == PRE_RT ? cov3D_precomp != nullptr : FORM::geo == PRE_GEO_COV3D;
+    const bool has_colors = FORM::col == PRE_RT ? colors_precomp != nullptr : FORM::col == PRE_COL_PRECOMP;
+    const bool staged_sh = FORM::col == PRE_RT ? (shs != nullptr && cam.M == 16) : FORM::col == PRE_COL_SH16;
     // bands of a quarter of the frame or more: still cheaper than a second latency phase (measured: 0.098 ms two-phase vs
     // 0.074 ms speculative for a quarter-frame band at 1 M Gaussians)
-    const bool speculative = (cam.tile_y1 - cam.tile_y0) * 4 >= cam.gy;
+    const bool speculative = FORM::spec == PRE_RT ? (cam.tile_y1 - cam.tile_y0) * 4 >= cam.gy : FORM::spec != 0;
+    const bool has_clamp = FORM::clamp == PRE_RT ? clamped_out != nullptr : FORM::clamp != 0;
     // wave-uniform trip count: every lane of a wave runs the same iterations (lanes past P idle inside)
     GsrFrameAcc acc;
     for (int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane; i0 < P; i0 += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = i0 + lane;
         const bool in_range = i < P;
+        // the previous trip's SH rows are read before this trip's block replaces them (a wave runs its LDS accesses in program order; this
+        // says so to the compiler, emits no instruction, and is what orders the lanes where each is a thread of its own: tests/simt)
+        __builtin_amdgcn_wave_barrier();
         GsrSplat sp;
         sp.radius = 0; sp.tiles = 0; sp.minx = sp.miny = sp.maxx = sp.maxy = 0; sp.depth = 0.f;
         float mean[3] = {0.f, 0.f, 0.f};
@@ -243,7 +270,7 @@ preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
             if (in_range) {     // the geometry loads ride in the same latency window
                 mean[0] = means3D[i * 3 + 0]; mean[1] = means3D[i * 3 + 1]; mean[2] = means3D[i * 3 + 2];
                 g_op = opacities[i];
-                if (!cov3D_precomp) {
+                if (!has_cov) {
                     g_s[0] = scales[i * 3 + 0]; g_s[1] = scales[i * 3 + 1]; g_s[2] = scales[i * 3 + 2];
                     g_rot = reinterpret_cast<const float4*>(rotations)[i];
                 }
@@ -257,7 +284,7 @@ preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
                 g_op = opacities[i];
             }
             float cov[6];
-            if (cov3D_precomp) {
+            if (has_cov) {
 #pragma unroll
                 for (int k = 0; k < 6; ++k) cov[k] = cov3D_precomp[i * 6 + k];
             } else {
@@ -288,7 +315,7 @@ preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
             float rgb[3] = {0.f, 0.f, 0.f};
             if (!need_color) {
                 // visible but outside the band: never blended here, record keeps geometry only
-            } else if (colors_precomp) {
+            } else if (has_colors) {
                 rgb[0] = colors_precomp[i * 3 + 0]; rgb[1] = colors_precomp[i * 3 + 1]; rgb[2] = colors_precomp[i * 3 + 2];
             } else if (staged_sh) {
                 if (SPLIT) gsr_sh_to_rgb_row(cam.sh_degree, 16, GsrShRowSplit{tile + SPLIT_DC + lane * 3, tile + lane * 45}, mean, cam.campos, rgb, clampbits);
@@ -310,7 +337,7 @@ preprocess_fwd_kernel(GsrCamDev camd, int P, const float* __restrict__ means3D, 
         splats[i * 4 + 3] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), 0.f, __uint_as_float(sp.tiles));
         rect[i] = rc;
         tiles[i] = sp.tiles;
-        if (clamped_out) clamped_out[i] = clampbits;
+        if (has_clamp) clamped_out[i] = clampbits;
         radii[i] = sp.radius;
         // depth-sort key (gsr_internal.h): 27 bits of bits(depth) - bits(0.2f); Gaussians with no tile in the band sort last.
         const uint32_t key = gsr_depth_key(sp.depth, sp.tiles != 0u, acc.ovf);
@@ -695,19 +722,62 @@ inline int stream_grid(int64_t n) {
     return (int)b;
 }
 
+// ---- forward: which instantiation, how many workgroups ----
+int g_preprocess_generic = 0;      // option preprocess_generic (A/B, tests): 1 = every call runs the generic instantiation
+int g_preprocess_hot_grid = 0;     // option preprocess_hot_grid (tuning): workgroups of the hot instantiations, 0 = from the occupancy
+int g_preprocess_last_path = 0;    // the most recent launch: 1 = generic, 2 = hot (test hook debug_last_preprocess_path)
+
+// Workgroups of a hot instantiation that are resident on the whole device at once (workgroups per CU, as the runtime computes them
+// for the code object that was really built, times the CUs), asked once per device and instantiation.  A grid of exactly that many
+// workgroups runs as one round; the 1024 of stream_grid would run as 768 + 256 at three workgroups per CU.  0: not known.
+template <bool SPLIT>
+int hot_resident_groups() {
+#ifdef GSR_SIMT_SHIM      // (tests/simt: no device to ask)
+    return 0;
+#else
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int> cached[MAX_DEV];      // 0 = not asked yet, < 0 = the query failed (every thread that asks stores the same answer)
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= MAX_DEV) return 0;
+    if (cached[d].load() == 0) {
+        int per_cu = 0, cus = 0;
+        const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, preprocess_fwd_kernel<SPLIT, GsrPreHot>, 256, 0) == hipSuccess &&
+                        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && per_cu > 0 && cus > 0;
+        cached[d].store(ok ? per_cu * cus : -1);
+    }
+    const int n = cached[d].load();
+    return n > 0 ? n : 0;
+#endif
+}
+
 }  // namespace
 
 int gsr_launch_preprocess(const GsrCamDev& cam, int P, const float* means3D, const float* shs,
                           const float* colors_precomp, const float* opacities, const float* scales,
                           const float* rotations, const float* cov3D_precomp, GsrGeom g, int32_t* radii,
                           const GsrFrameStatsDev& fs, hipStream_t st) {
-    const int grid = stream_grid(P) < GSR_FRAME_MAX_GROUPS ? stream_grid(P) : GSR_FRAME_MAX_GROUPS;      // (gsr_frame.h: tickets)
-#define GSR_PRE_FWD(SPLIT_)                                                                                                            \
-    hipLaunchKernelGGL((preprocess_fwd_kernel<SPLIT_>), dim3(grid), dim3(256), 0, st, cam, P, means3D, shs, colors_precomp,              \
+    // the hot form (GsrPreHot): what the kernel's generic instantiation finds out per trip, decided here once
+    const bool hot = !g_preprocess_generic && !cov3D_precomp && !colors_precomp && shs && scales && rotations && cam.M == 16 &&
+                     (cam.tile_y1 - cam.tile_y0) * 4 >= cam.gy;
+    int grid = stream_grid(P);
+    if (hot) {
+        const int want = g_preprocess_hot_grid > 0 ? g_preprocess_hot_grid : (cam.sh_dc ? hot_resident_groups<true>() : hot_resident_groups<false>());
+        const int64_t blocks = ((int64_t)P + 255) / 256;
+        if (want > 0) grid = (int)(blocks < want ? (blocks < 1 ? 1 : blocks) : want);
+    }
+    if (grid > GSR_FRAME_MAX_GROUPS) grid = GSR_FRAME_MAX_GROUPS;      // (gsr_frame.h: tickets)
+    g_preprocess_last_path = hot ? 2 : 1;
+#define GSR_PRE_FWD(SPLIT_, FORM_)                                                                                                     \
+    hipLaunchKernelGGL((preprocess_fwd_kernel<SPLIT_, FORM_>), dim3(grid), dim3(256), 0, st, cam, P, means3D, shs, colors_precomp,       \
                        opacities, scales, rotations, cov3D_precomp, g.splats, g.rect, g.tiles,                                         \
                        /*clamped (recomputed by the backward)*/ nullptr, g.keys[0], g.vals[0], radii, fs)
-    if (cam.sh_dc) GSR_PRE_FWD(true);
-    else GSR_PRE_FWD(false);
+    if (cam.sh_dc) {
+        if (hot) GSR_PRE_FWD(true, GsrPreHot);
+        else GSR_PRE_FWD(true, GsrPreGeneric);
+    } else {
+        if (hot) GSR_PRE_FWD(false, GsrPreHot);
+        else GSR_PRE_FWD(false, GsrPreGeneric);
+    }
 #undef GSR_PRE_FWD
     return grid;
 }
@@ -766,3 +836,6 @@ void gsr_launch_mark_visible(int P, const float* means3D, const float* view, uin
 
 
 void gsr_set_preprocess_grid_cap(int cap) { g_stream_grid_cap = cap < 64 ? 64 : cap; }
+void gsr_set_preprocess_generic(int on) { g_preprocess_generic = on ? 1 : 0; }
+void gsr_set_preprocess_hot_grid(int groups) { g_preprocess_hot_grid = groups < 0 ? 0 : groups; }
+int gsr_preprocess_last_path(void) { return g_preprocess_last_path; }

@@ -686,6 +686,11 @@ int gsr_profile_trace(uint64_t* out, int max_waves);
  * and ssim_variant (0 = marching-wave SSIM / training-loss kernels, 1 = the LDS-tiled form), ssim_target_waves (launch shape of
  * the marching form: the waves a launch aims for, forward and backward alike, at least 256; 0 = back to the defaults of 4096
  * forward / 2048 backward, which no single value expresses), preprocess_grid_cap.
+ *   preprocess_generic  0 (default) = the forward per-Gaussian kernel runs the instantiation compiled for the call form (scales + rotations,
+ *                    16-coefficient SH fused or dc / rest, band of a quarter of the frame or more: no dead paths), 1 = always the generic one
+ *                    (A/B and tests; the same bits either way)
+ *   preprocess_hot_grid workgroups of those instantiations: 0 (default) = one resident round, from the occupancy the runtime reports; 1..2047
+ * Test hook: debug_last_preprocess_path = 1 (generic) / 2 (hot) changes nothing and succeeds iff the most recent forward took that instantiation.
  * Test hook: debug_dirty_control_block = t preloads t tickets into the frame counter of the NEXT forward call, once (a counter that is
  * not zero when a frame begins, csrc/gsr_frame.h): that frame is wrong or refused, the ones after it must be right again. */
 int gsr_set_option(const char* name, int value);

@@ -119,7 +119,57 @@ def forward_walk_step(extra=()):
     return mix
 
 
+def preprocess_forward(source=None, extra=()):
+    """Every instantiation of the forward per-Gaussian kernel (csrc/preprocess.hip preprocess_fwd_kernel<SPLIT, FORM>), one dict each:
+    from the code-object metadata the VGPRs, the spilled SGPRs (parked in VGPR lanes) and VGPRs (in scratch), scratch and LDS bytes; the
+    waves per SIMD the compiler states for that register count and the workgroups per CU the LDS admits; and static counts over the whole
+    kernel: VALU, SALU, v_mov_b32, lane moves (v_readlane / v_writelane: the traffic of the parked SGPRs), global loads and stores.
+    `source`: another copy of preprocess.hip (the parent's, for the committed before / after pair in profiles/); same flags, same headers.
+        python tools/isa_audit.py preprocess_forward [path/to/preprocess.hip]      # prints JSON"""
+    src = source or os.path.join(CSRC, "preprocess.hip")
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only",
+               "-o", out, src] + UNITS["preprocess.hip"] + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(r.stderr[-2000:])
+        s = open(out).read()
+    meta = {}
+    for entry in re.split(r"^  - (?=\.)", s[s.index("amdhsa.kernels:"):], flags=re.M)[1:]:
+        f = dict(re.findall(r"^\s*\.(\w+):\s*(\S+)\s*$", entry, re.M))
+        meta[f["name"]] = f
+    rows = []
+    for m in re.finditer(r"^(_Z\w*preprocess_fwd_kernel\w+): ; @.*?\n(.*?)^\.Lfunc_end\d+:(.*?^; Occupancy:\s*\d+)", s, re.S | re.M):
+        name, body, trailer = m.group(1), m.group(2), m.group(3)
+        f = meta[name]
+        ops = [t[0] for t in (line.strip().split() for line in body.split("\n")) if t and not t[0].startswith((";", ".")) and not t[0].endswith(":")]
+        form = re.search(r"GsrPreFormIL(\w+?)EEE", name)
+        form = "generic" if form is None or "n1" in form.group(1) and form.group(1).count("n1") == 4 else "hot" if form.group(1) == "i0ELi0ELi1ELi0" else form.group(1)
+        occ = re.search(r"; Occupancy:\s*(\d+)", trailer)
+        lds = int(f["group_segment_fixed_size"])
+        rows.append({
+            "kernel": name, "split_sh": "ILb1E" in name, "form": form,
+            "vgprs": int(f["vgpr_count"]), "agprs": int(f.get("agpr_count", 0)), "sgprs": int(f["sgpr_count"]),
+            "sgpr_spill_count": int(f["sgpr_spill_count"]), "vgpr_spill_count": int(f["vgpr_spill_count"]),
+            "scratch_bytes": int(f["private_segment_fixed_size"]), "lds_bytes": lds,
+            "waves_per_simd": int(occ.group(1)) if occ else None, "workgroups_per_cu_by_lds": (160 * 1024) // lds if lds else None,
+            "valu": sum(o.startswith("v_") for o in ops), "salu": sum(o.startswith("s_") and o not in ("s_waitcnt", "s_nop") for o in ops),
+            "v_mov_b32": ops.count("v_mov_b32_e32") + ops.count("v_mov_b32_e64") + ops.count("v_mov_b32"),
+            "lane_moves": sum(o.startswith(("v_readlane", "v_writelane")) for o in ops),
+            "global_loads": sum(o.startswith("global_load") for o in ops), "global_stores": sum(o.startswith("global_store") for o in ops),
+        })
+    if not rows:
+        raise RuntimeError("no preprocess_fwd_kernel instantiation found")
+    return sorted(rows, key=lambda r: (r["form"] != "hot", r["split_sh"]))
+
+
 def main():
+    if sys.argv[1:2] == ["preprocess_forward"]:
+        import json
+        srcs = [a for a in sys.argv[2:] if not a.startswith("-")]
+        print(json.dumps({"unit": "preprocess.hip", "flags": UNITS["preprocess.hip"], "instantiations": preprocess_forward(srcs[0] if srcs else None, [a for a in sys.argv[2:] if a.startswith("-")])}, indent=1))
+        return
     files = [a for a in sys.argv[1:] if a.endswith(".hip")]
     extra = [a for a in sys.argv[1:] if a.startswith("-")]
     if not files:
