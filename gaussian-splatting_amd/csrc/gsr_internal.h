@@ -345,6 +345,10 @@ void gsr_launch_absgrad_from_records(int P, int W, int H, const float* splat_gra
 static inline size_t gsr_bg_grad_blocks(int64_t npix) { return (size_t)((npix + GSR_BG_GRAD_PIXELS - 1) / GSR_BG_GRAD_PIXELS); }
 void gsr_launch_bg_grad(int64_t npix, int W, int row0, int row1, const float* final_T, const float* dL_dpix, float* dL_dbg_image,
                         float* dL_dbg, double* partials, hipStream_t st);
+// Clears the flag words of the R instances and, given block_steps and tile_order (both non-NULL), sorts the band's tiles (order_mode 1, 2) or half
+// tiles (3) by the forward's step counts, heaviest first, into tile_order in the same launch.  Returns whether tile_order was written.
+bool gsr_launch_bwd_plan(const GsrCamDev& cam, const uint32_t* block_steps, uint32_t* tile_order, uint32_t* inst_flag, int64_t R, int order_mode,
+                         hipStream_t st);
 size_t gsr_reduce_units(int64_t R);      // units of 1024 instance records the reduce works in
 void gsr_launch_reduce_instances(int P, int64_t R, const uint32_t* order, const uint32_t* offsets, const float4* splats,
                                  const float* inst_grads, const uint32_t* inst_flag, float* splat_grads, uint2* unit_first,
@@ -394,6 +398,11 @@ void gsr_launch_render_features(const GsrCamDev& cam, const GsrSavedFrame& f, co
 void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out, hipStream_t st);
 void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* dL_dout, int C,
                                          const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st);
+// feature_geom.hip: the walks of gsr_render_features_backward_geometry, one per channel group on the stream.  They clear the flag words of the R
+// instances and leave the blend backward's instance records (words 0..5: the five moments and the zeroth moment; 6..11 zero) in inst_grads / inst_flag
+// of a GsrBwdScratch; gsr_launch_reduce_instances on the same stream turns them into the [P,12] rows.  R > 0.
+void gsr_launch_feature_geometry_walks(const GsrCamDev& cam, int64_t R, const GsrSavedFrame& f, int order_mode /*the blend backward's: 0 = index order*/,
+                                       const float* features, const float* dL_dout, int C, float* inst_grads, uint32_t* inst_flag, hipStream_t st);
 
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,

@@ -811,6 +811,22 @@ int gsr_render_backward_variant_available(int variant) {
 #endif
 }
 
+bool gsr_launch_bwd_plan(const GsrCamDev& cam, const uint32_t* block_steps, uint32_t* tile_order, uint32_t* inst_flag, int64_t R, int order_mode,
+                         hipStream_t st) {
+    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    // instances that contributed nowhere get no record: only their flag words are cleared (the caller's scratch is carved in
+    // 128-byte steps, so whole 16-byte words belong to the flag array)
+    const int64_t n16 = (R * 4 + 15) / 16;
+    if (tile_order && block_steps) {
+        const int fill_blocks = (int)std::min<int64_t>(2048, (n16 + PLAN_THREADS - 1) / PLAN_THREADS);
+        hipLaunchKernelGGL(bwd_plan_kernel, dim3(1 + fill_blocks), dim3(PLAN_THREADS), 0, st, cam.tile_y0 * cam.gx, n_band_tiles,
+                           reinterpret_cast<const uint4*>(block_steps), tile_order, reinterpret_cast<uint4*>(inst_flag), n16, order_mode);
+        return true;
+    }
+    (void)hipMemsetAsync(inst_flag, 0, (size_t)R * 4, st);
+    return false;
+}
+
 namespace {
 // body of the three launchers below (comp_in may be NULL: the plain call)
 void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uint32_t* point_list,
@@ -845,17 +861,7 @@ void launch_render_backward(const GsrCamDev& cam, const uint2* ranges, const uin
 #endif
     (void)variant; (void)splat_grads; (void)groups;
     const int groups16 = (n_band_tiles + 15) / 16;
-    // instances that contributed nowhere get no record: only their flag words are cleared (the caller's scratch is carved in
-    // 128-byte steps, so whole 16-byte words belong to the flag array)
-    const int64_t n16 = (R * 4 + 15) / 16;
-    if (tile_order && block_steps) {
-        const int fill_blocks = (int)std::min<int64_t>(2048, (n16 + PLAN_THREADS - 1) / PLAN_THREADS);
-        hipLaunchKernelGGL(bwd_plan_kernel, dim3(1 + fill_blocks), dim3(PLAN_THREADS), 0, st, cam.tile_y0 * cam.gx, n_band_tiles,
-                           reinterpret_cast<const uint4*>(block_steps), tile_order, reinterpret_cast<uint4*>(inst_flag), n16, order_mode);
-    } else {
-        tile_order = nullptr;
-        (void)hipMemsetAsync(inst_flag, 0, (size_t)R * 4, st);
-    }
+    if (!gsr_launch_bwd_plan(cam, block_steps, tile_order, inst_flag, R, order_mode, st)) tile_order = nullptr;
     const int wave_order = (tile_order && order_mode == 3) ? 1 : 0;
     auto walk = dL_dinvdepth ? (absgrad ? render_bwd_half<true, true> : render_bwd_half<true, false>)
                              : (absgrad ? render_bwd_half<false, true> : render_bwd_half<false, false>);

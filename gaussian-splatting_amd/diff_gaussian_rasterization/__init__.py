@@ -380,6 +380,7 @@ class _SavedState(NamedTuple):
     P: int
     fwd: _Forward
     device: torch.device
+    node: object = None      # the _RasterizeGaussians node itself (render_features(geometry=True): its inputs and per-Gaussian state)
 
 
 def _saved_state(rendered, who: str, standalone: str) -> _SavedState:
@@ -398,7 +399,7 @@ def _saved_state(rendered, who: str, standalone: str) -> _SavedState:
     except RuntimeError as e:
         raise GsrError(f"the rasterizer call's state has been freed: call {who} before backward(), or use retain_graph=True") from e
     means3D, geom, binning, img = saved[0], saved[8], saved[9], saved[10]
-    return _SavedState(ctx.raster_settings, ctx.tile_rows, int(means3D.shape[0]), _Forward(geom, binning, img, ctx.num_rendered), means3D.device)
+    return _SavedState(ctx.raster_settings, ctx.tile_rows, int(means3D.shape[0]), _Forward(geom, binning, img, ctx.num_rendered), means3D.device, ctx)
 
 
 def contribution_stats(rendered: torch.Tensor, pixel_weight: Optional[torch.Tensor] = None,
@@ -485,17 +486,8 @@ class _RenderFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, geom, binning, img, num_rendered, raster_settings, tile_rows):
-        lib = _lib.load()
-        device = features.device
         P, Cn = int(features.shape[0]), int(features.shape[1])
-        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
-        f = _f32c(features.detach())
-        out = torch.zeros(Cn, H, W, dtype=torch.float32, device=device)      # (with `tile_rows` the library leaves pixels outside the band untouched)
-        keep: list = []
-        with torch.cuda.device(device):
-            s = _make_settings(raster_settings, keep, tile_rows, bg_image=True)
-            _lib.check(lib.gsr_render_features(C.byref(s), P, num_rendered, _ptr(geom), _ptr(binning), _ptr(img), _ptr(f), Cn, _ptr(out),
-                                               _stream_ptr(device)), "gsr_render_features")
+        out = _features_forward(features, _Forward(geom, binning, img, num_rendered), raster_settings, tile_rows)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(geom, binning, img)
             ctx.num_rendered, ctx.raster_settings, ctx.tile_rows, ctx.shape, ctx.dtype = num_rendered, raster_settings, tile_rows, (P, Cn), features.dtype
@@ -503,35 +495,157 @@ class _RenderFeatures(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         geom, binning, img = ctx.saved_tensors
-        P, Cn = ctx.shape
-        device = grad_out.device
-        g = _f32c(grad_out)
-        grad = torch.empty(P, Cn, dtype=torch.float32, device=device)
-        keep: list = []
-        with torch.cuda.device(device):
-            s = _make_settings(ctx.raster_settings, keep, ctx.tile_rows, bg_image=True)
-            scratch = torch.empty(_sized("contrib", device, lib.gsr_feature_grad_scratch_bytes(P, ctx.num_rendered, Cn)), dtype=torch.uint8, device=device)
-            _lib.check(lib.gsr_render_features_backward(C.byref(s), P, ctx.num_rendered, _ptr(geom), _ptr(binning), _ptr(img), _ptr(g), Cn,
-                                                        _ptr(scratch), _ptr(grad), _stream_ptr(device)), "gsr_render_features_backward")
+        grad = _features_backward(grad_out, ctx.shape, _Forward(geom, binning, img, ctx.num_rendered), ctx.raster_settings, ctx.tile_rows)
         return grad.to(ctx.dtype), None, None, None, None, None, None
 
 
-def render_features(rendered: torch.Tensor, features: torch.Tensor) -> torch.Tensor:
+def _features_forward(features, fwd: _Forward, raster_settings, tile_rows) -> torch.Tensor:
+    """gsr_render_features on the state a tracking forward left -> F[C,H,W] (fp32)."""
+    lib = _lib.load()
+    device = features.device
+    P, Cn = int(features.shape[0]), int(features.shape[1])
+    H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+    f = _f32c(features.detach())
+    out = torch.zeros(Cn, H, W, dtype=torch.float32, device=device)      # (with `tile_rows` the library leaves pixels outside the band untouched)
+    keep: list = []
+    with torch.cuda.device(device):
+        s = _make_settings(raster_settings, keep, tile_rows, bg_image=True)
+        _lib.check(lib.gsr_render_features(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(f), Cn, _ptr(out),
+                                           _stream_ptr(device)), "gsr_render_features")
+    return out
+
+
+def _features_backward(grad_out, shape, fwd: _Forward, raster_settings, tile_rows) -> torch.Tensor:
+    """gsr_render_features_backward -> dL/dfeatures [P,C] (fp32)."""
+    lib = _lib.load()
+    P, Cn = shape
+    device = grad_out.device
+    g = _f32c(grad_out)
+    grad = torch.empty(P, Cn, dtype=torch.float32, device=device)
+    keep: list = []
+    with torch.cuda.device(device):
+        s = _make_settings(raster_settings, keep, tile_rows, bg_image=True)
+        scratch = torch.empty(_sized("contrib", device, lib.gsr_feature_grad_scratch_bytes(P, fwd.num_rendered, Cn)), dtype=torch.uint8, device=device)
+        _lib.check(lib.gsr_render_features_backward(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(g), Cn,
+                                                    _ptr(scratch), _ptr(grad), _stream_ptr(device)), "gsr_render_features_backward")
+    return grad
+
+
+class _FeatureFrame(NamedTuple):
+    """The frame a feature render with geometry gradients stands on: the state of its tracking forward and the per-Gaussian inputs of that forward as
+    the C ABI took them (fp32, contiguous; None where the call had none)."""
+    settings: GaussianRasterizationSettings
+    tile_rows: Optional[Tuple[int, int]]
+    fwd: _Forward
+    radii: torch.Tensor
+    means3D: torch.Tensor
+    opacities: torch.Tensor
+    scales: Optional[torch.Tensor]
+    rotations: Optional[torch.Tensor]
+    cov3D: Optional[torch.Tensor]
+
+
+def _feature_geometry_records(frame: _FeatureFrame, features, grad_out) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """gsr_render_features_backward_geometry -> (the [P,12] records, a view into the scratch returned beside it; None for P == 0)."""
+    lib = _lib.load()
+    device = grad_out.device
+    P, Cn = int(features.shape[0]), int(features.shape[1])
+    fwd = frame.fwd
+    keep: list = []
+    s = _make_settings(frame.settings, keep, frame.tile_rows, bg_image=True)
+    scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
+    rec_ptr = C.c_void_p(0)
+    _lib.check(lib.gsr_render_features_backward_geometry(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img),
+                                                         _ptr(features), _ptr(grad_out), Cn, _ptr(scratch), C.byref(rec_ptr), _stream_ptr(device)),
+               "gsr_render_features_backward_geometry")
+    if P == 0:
+        return None, scratch
+    off = int(rec_ptr.value) - scratch.data_ptr()
+    return scratch[off:off + P * 48].view(torch.float32).view(P, 12), scratch
+
+
+def _geometry_from_records(frame: _FeatureFrame, records, device):
+    """The per-Gaussian backward on records whose colour words are zero, in its `colors_precomp` form with a zero colour tensor: no [P,M,3] SH
+    gradient is allocated or written.  -> _gradients' list."""
+    P = int(frame.means3D.shape[0])
+    grads, _ = _gradients(P, device, True, frame.cov3D is not None, None, False, frame.scales is not None, frame.rotations is not None)
+    keep: list = []
+    s = _make_settings(frame.settings, keep, frame.tile_rows, bg_image=True)
+    inputs = (frame.means3D, None, torch.zeros(P, 3, dtype=torch.float32, device=device), frame.opacities, frame.scales, frame.rotations, frame.cov3D)
+    _backward_preprocess(s, P, 0, inputs, frame.radii, frame.fwd.geom, records, grads, device)
+    return grads
+
+
+class _RenderFeaturesGeometry(torch.autograd.Function):
+    """_RenderFeatures that is also differentiable in the geometry of its frame: inputs are `features` and the caller's own means3D, means2D, opacities,
+    scales, rotations, cov3D_precomp (None where the rasterizer call had none).  F has _RenderFeatures' bits.  The backward runs
+    gsr_render_features_backward for `features`, and for the geometry gsr_render_features_backward_geometry followed by the per-Gaussian backward
+    (gsr_backward_preprocess); what nobody needs is not computed.  The camera is a constant on this path."""
+
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3D, frame: _FeatureFrame):
+        out = _features_forward(features, frame.fwd, frame.settings, frame.tile_rows)
+        if any(ctx.needs_input_grad[:7]):
+            ctx.frame = frame
+            ctx.features = _f32c(features.detach()) if any(ctx.needs_input_grad[1:7]) else None
+            ctx.shape, ctx.dtype = (int(features.shape[0]), int(features.shape[1])), features.dtype
+            ctx.meta = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in (means3D, means2D, opacities, scales, rotations, cov3D))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        frame = ctx.frame
+        device = grad_out.device
+        need = ctx.needs_input_grad
+        g = _f32c(grad_out)
+        d_features = None
+        if need[0]:
+            d_features = _features_backward(g, ctx.shape, frame.fwd, frame.settings, frame.tile_rows).to(ctx.dtype)
+        out = [None] * 6
+        if any(need[1:7]) and ctx.shape[0] > 0:
+            with torch.cuda.device(device):
+                records, _scratch = _feature_geometry_records(frame, ctx.features, g)
+                dm2, _, dop, dm3, dcov, _, dsc, drot = _geometry_from_records(frame, records, device)
+            for k, t in enumerate((dm3, dm2, dop, dsc, drot, dcov)):
+                if need[1 + k] and ctx.meta[k] is not None and t is not None:
+                    out[k] = t.view(ctx.meta[k][0]).to(ctx.meta[k][1])
+        elif any(need[1:7]):
+            out = [None if (m is None or not need[1 + k]) else torch.zeros(m[0], dtype=m[1], device=device) for k, m in enumerate(ctx.meta)]
+        return (d_features, *out, None)
+
+
+def _geometry_frame(st: _SavedState) -> Tuple[_FeatureFrame, tuple]:
+    """(the frame behind a rasterizer call as _RenderFeaturesGeometry takes it, the caller's own geometry tensors of that call)."""
+    saved = st.node.saved_tensors
+    has_sh, has_col, has_sc, has_rot, has_cov = st.node.flags
+    frame = _FeatureFrame(st.settings, st.tile_rows, st.fwd, saved[7], saved[0], saved[3], saved[4] if has_sc else None, saved[5] if has_rot else None,
+                          saved[6] if has_cov else None)
+    return frame, st.node.geom_inputs
+
+
+def render_features(rendered: torch.Tensor, features: torch.Tensor, geometry: bool = False) -> torch.Tensor:
     """-> F[C,H,W] = sum_g w_gp features[g,c]: N-channel per-Gaussian features (language / semantic fields, distillation heads, label votes) blended
     with the weights w = alpha * T of a frame that has ALREADY been rendered (no reference counterpart; include/gsr.h gsr_render_features).
     `rendered` and the state it is read from are `contribution_stats`'s: any tensor computed from one rasterizer call's outputs with gradients
     enabled, before that call's `backward()` frees the state (or with `retain_graph=True`); no second forward, whatever C is.  `features` is
     [P,C], 1 <= C <= 1024.  There is NO background term and no normalisation: compose with the alpha image of `return_alpha=True`.
-    Differentiable in `features` ONLY: geometry and opacity are constants of the frame already rendered, so no gradient reaches means3D,
-    scales, rotations or opacities through F (train those through the colour render).  The backward keeps its own references to the state: it
-    still runs after the frame's own `backward()`.  Rows of Gaussians that contribute nowhere never reach the image and get exact zero
-    gradients.  With `tile_rows`, pixels outside the band are 0 and the gradient is the band's.  Two calls give the same bits, and channel c has
-    the bits of a call on column c alone."""
+    With `geometry=False` (the default) differentiable in `features` ONLY: geometry and opacity are constants of the frame already rendered, so
+    no gradient reaches means3D, scales, rotations or opacities through F.  With `geometry=True` (joint training of a field and its geometry,
+    depth / normal supervision through a rendered z or normal column; include/gsr.h gsr_render_features_backward_geometry) F has the same bits
+    and its backward also delivers gradients to the tensors that were PASSED TO THE RASTERIZER CALL behind `rendered` -- means3D, opacities,
+    scales + rotations or cov3D_precomp, and means2D if it was passed (so the feature loss counts in the densification statistics) -- which
+    autograd adds to what the colour loss delivers.  The camera stays a constant on this path: no gradient reaches viewmatrix / projmatrix /
+    campos through F.  The backward keeps its own references to the state: it still runs after the frame's own `backward()`.  Rows of Gaussians
+    that contribute nowhere never reach the image (they may hold anything) and get exact zero gradients.  With `tile_rows`, pixels outside the
+    band are 0 and the gradients are the band's.  Two calls give the same bits, and channel c of F and of dL/dfeatures has the bits of a call on
+    column c alone."""
     st = _saved_state(rendered, "render_features", "features")
     features = _feature_rows(features, st.P, st.device)
-    return _RenderFeatures.apply(features, st.fwd.geom, st.fwd.binning, st.fwd.img, st.fwd.num_rendered, st.settings, st.tile_rows)
+    if not geometry:
+        return _RenderFeatures.apply(features, st.fwd.geom, st.fwd.binning, st.fwd.img, st.fwd.num_rendered, st.settings, st.tile_rows)
+    frame, (means3D, means2D, opacities, scales, rotations, cov3D) = _geometry_frame(st)
+    return _RenderFeaturesGeometry.apply(features, means3D, means2D, opacities, scales, rotations, cov3D, frame)
 
 
 def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
@@ -659,6 +773,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.absgrad and grad_sync is not None:
             raise GsrError("absgrad is not supported together with grad_sync (multi-GPU renderers): use the single-GPU rasterizer for it")
         ctx.means2D_ref = means2D if ctx.absgrad else None      # the caller's own tensor: backward sets its .absgrad
+        # the caller's own geometry tensors (the saved ones are converted copies when an fp32 / contiguity conversion happened):
+        # render_features(geometry=True) sends its gradients to these
+        ctx.geom_inputs = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp)
         # the composite entry point only when something beyond the reference's contract is asked for
         composite = bool(return_alpha) or ctx.bg_image or ctx.bg_grad
         keep: list = []
@@ -925,18 +1042,23 @@ class GaussianRasterizer(nn.Module):
             s, P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
             return _pixel_probe(s, P, fwd, threshold, int(rs.image_height), int(rs.image_width), device), radii
 
-    def features(self, means3D, opacities, features, scales=None, rotations=None, cov3D_precomp=None):
+    def features(self, means3D, opacities, features, scales=None, rotations=None, cov3D_precomp=None, geometry: bool = False):
         """-> (F[C,H,W], radii[P]): `render_features` for this camera without a render of one's own to hand (no reference counterpart): runs a
         tracking forward with zero colours under no_grad, honours `tile_rows`, then blends `features` [P,C] with its weights.  Differentiable in
-        `features` only: no gradient reaches the geometry or the opacities through F."""
+        `features` only: no gradient reaches the geometry or the opacities through F -- unless `geometry=True`, which makes F (same bits)
+        differentiable in means3D, opacities and scales + rotations / cov3D_precomp as well (`render_features`)."""
         _lib.load()
         _require_cuda(means3D, "means3D")
         device = means3D.device
         features = _feature_rows(features, int(means3D.shape[0]), device)
+        tile_rows = getattr(self, "tile_rows", None)
         with torch.no_grad(), torch.cuda.device(device):
             _s, _P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
-        return _RenderFeatures.apply(features, fwd.geom, fwd.binning, fwd.img, fwd.num_rendered, self.raster_settings,
-                                     getattr(self, "tile_rows", None)), radii
+        if not geometry:
+            return _RenderFeatures.apply(features, fwd.geom, fwd.binning, fwd.img, fwd.num_rendered, self.raster_settings, tile_rows), radii
+        c = lambda t: _f32c(t.detach()) if t is not None else None      # noqa: E731  (what the tracking forward read)
+        frame = _FeatureFrame(self.raster_settings, tile_rows, fwd, radii, c(means3D), c(opacities), c(scales), c(rotations), c(cov3D_precomp))
+        return _RenderFeaturesGeometry.apply(features, means3D, None, opacities, scales, rotations, cov3D_precomp, frame), radii
 
 
 class SparseGaussianAdam(torch.optim.Adam):

@@ -131,6 +131,7 @@ SIGNATURES = {
     "gsr_render_features": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 4 + [C.c_int, _vp, _vp]),
     "gsr_feature_grad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "gsr_render_features_backward": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 4 + [C.c_int, _vp, _vp, _vp]),
+    "gsr_render_features_backward_geometry": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.c_int, _vp, C.POINTER(C.c_void_p), _vp]),
     "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
     "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
     "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

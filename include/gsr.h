@@ -369,7 +369,8 @@ int gsr_pixel_probe(const GsrRasterSettings* settings, int P, int32_t num_render
  *   gsr_render_features            out[c,p] = sum_g w_gp features[g,c], fp32 in list order.  NO background term and no normalisation: compose
  *                                  with the alpha image of gsr_rasterize_forward_composite (1 - alpha is the weight of a background).
  *   gsr_render_features_backward   dL_dfeatures[g,c] = sum_p w_gp dL_dout[c,p]: the gradient with respect to `features` ONLY.  Geometry and
- *                                  opacity are constants of the frame already rendered; gradients to them through `out` are not computed.
+ *                                  opacity are constants of the frame already rendered; gradients to them through `out` are the business
+ *                                  of gsr_render_features_backward_geometry below.
  * features / dL_dfeatures are [P,C] row-major, out / dL_dout planar [C,H,W], 1 <= C <= GSR_MAX_FEATURE_CHANNELS.  Rows of `features` of
  * Gaussians that contribute nowhere (culled, hidden) are never multiplied into the image -- they may hold anything -- and their rows of
  * dL_dfeatures are exact zeros; every one of the P rows is written.  Every pixel of the band inside the image is written (zeros without a
@@ -391,6 +392,32 @@ int gsr_render_features_backward(const GsrRasterSettings* settings, int P, int32
                                  const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                                  const float* dL_dout /* [C,H,W] */, int C, void* scratch,
                                  float* dL_dfeatures /* [P,C] */, void* stream);
+/*
+ * Geometry and opacity gradients THROUGH the feature render (joint training of a field and its geometry; depth or normal supervision, where the
+ * loss on a rendered z or normal column must move the Gaussians): the per-Gaussian [P,12] records of gsr_backward_blend for the loss
+ * L(out), out = gsr_render_features(features).  Contributor rule as above.  Front to back over the contributors i of pixel p, with
+ * T_i = prod_{j<i} (1 - alpha_j), w_i = alpha_i T_i and g_c = dL_dout[c,p]:
+ *     s_i       = sum_c features[id_i,c] g_c
+ *     dL/dalpha_i = T_i s_i - (sum_{j>i} w_j s_j) / (1 - alpha_i)        (no background / T_final term: `out` has none)
+ *     m_i       = opacity_i G_i dL/dalpha_i                              (uncapped opacity * G, straight through the 0.99 cap, as for colour)
+ * and per Gaussian, summed over the pixels of the band, (dx,dy) = mean2D - pixel, conic (A,B,C):
+ *     word 0 dL/dpx = sum m (-A dx - B dy)   word 1 dL/dpy = sum m (-C dy - B dx)   (pixel units, like gsr_backward_blend)
+ *     word 2 dL/dA = -1/2 sum m dx^2         word 3 dL/dB = -sum m dx dy            word 4 dL/dC = -1/2 sum m dy^2
+ *     word 5 dL/dopacity = sum G dL/dalpha   words 6..11 = 0
+ * i.e. words 0..5 and the layout of gsr_backward_blend's records: gsr_backward_preprocess follows unchanged and chains them to means3D /
+ * scales / rotations / cov3D / opacity / means2D (its colour and SH gradients are zero).  No gradient through culling, radii, tile assignment,
+ * depth order or the two cut-offs.  Rows of Gaussians without a contributing pixel are exact zeros, and their rows of `features` may hold
+ * anything, NaN included: s_i is taken under the pair's predicate.  With a band of tile rows the records are the band's contribution.
+ * P == 0 or num_rendered == 0: zero rows (P == 0: *splat_grads_out = NULL), and the state buffers are not read.  Fp32, no atomics, every sum
+ * in a fixed order: two runs give the same bits.  The states of the record entry points are not supported.
+ * `bwd_scratch`: gsr_backward_scratch_bytes(P, num_rendered) bytes, 16-byte aligned; *splat_grads_out points into it.  Argument checks as
+ * gsr_render_features_backward; NULL features / dL_dout / bwd_scratch with P > 0 and a NULL splat_grads_out are GSR_ERR_INVALID_ARG.
+ */
+int gsr_render_features_backward_geometry(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                                          const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                          const float* features /* [P,C] */, const float* dL_dout /* [C,H,W] */, int C,
+                                          void* bwd_scratch /* gsr_backward_scratch_bytes(P, num_rendered) */,
+                                          float** splat_grads_out, void* stream);
 
 /*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
