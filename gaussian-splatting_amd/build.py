@@ -7,7 +7,8 @@ Translation units and their flags:
   sort.hip, depthsort.hip, binning.hip (integer)
   render_fwd.hip, render_bwd.hip,
   contrib.hip, probe.hip, absgrad.hip,
-  features.hip, feature_geom.hip       (FMA contraction allowed; image tolerance 1e-5; what they must compute identically -- box
+  features.hip, feature_geom.hip,
+  distortion.hip                       (FMA contraction allowed; image tolerance 1e-5; what they must compute identically -- box
                                         test, exponent / alpha -- is csrc/gsr_blend.h, their wave reductions csrc/gsr_wave.h)
   gsr_api.cpp                          (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
@@ -50,6 +51,7 @@ UNITS = [
     ("absgrad.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("features.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("feature_geom.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
+    ("distortion.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("adam.hip", ["-ffp-contract=off"]),
     # no SLP vectorisation: the auto-packed v_pk_fma_f32 and the v_mov shuffles that assemble their operand pairs cost more
     # issue slots than the scalar FMAs they replace (forward 60.2 -> 55.3 us on one box); the per-Gaussian kernels were

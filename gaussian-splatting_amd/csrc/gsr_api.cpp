@@ -1335,6 +1335,64 @@ int gsr_render_features_backward_geometry(const GsrRasterSettings* settings, int
     return GSR_OK;
 }
 
+int gsr_distortion(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                   const void* image_buffer, const GsrDistortionOut* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const char* own = !out                                             ? "out (GsrDistortionOut) is NULL"
+                      : !out->distortion                               ? "GsrDistortionOut.distortion is NULL"
+                      : (out->depth_mode != 0 && out->depth_mode != 1) ? "GsrDistortionOut.depth_mode must be 0 (z) or 1 (1/z)"
+                                                                       : nullptr;
+    GsrCamDev cam;
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
+    if (rc != GSR_OK) return rc;
+    const int64_t R = num_rendered;
+    if (P == 0 || R == 0) {      // no state to read: zeros over the band
+        gsr_launch_distortion_defaults(cam, out->distortion, out->saved, st);
+        HIP_OK(hipGetLastError());
+        return GSR_OK;
+    }
+    gsr_launch_distortion(cam, saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer), out->distortion, out->saved, out->depth_mode, st);
+    STAGE_CHECK("distortion");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_distortion_backward(const GsrRasterSettings* settings, int P, int32_t num_rendered, const void* geom_buffer, const void* binning_buffer,
+                            const void* image_buffer, const float* dL_ddistortion, const float* saved, int depth_mode, void* bwd_scratch,
+                            float** splat_grads_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    GsrCamDev cam;
+    const char* own = (depth_mode != 0 && depth_mode != 1) ? "depth_mode must be 0 (z) or 1 (1/z)"
+                      : !splat_grads_out                   ? "splat_grads_out is NULL"
+                                                           : nullptr;
+    int rc = reader_args(settings, P, num_rendered, geom_buffer, binning_buffer, image_buffer, own, cam);
+    if (rc != GSR_OK) return rc;
+    *splat_grads_out = nullptr;
+    if (P > 0 && !bwd_scratch) return fail(GSR_ERR_INVALID_ARG, "bwd_scratch is NULL (gsr_backward_scratch_bytes)");
+    if (((uintptr_t)bwd_scratch) & 15) return fail(GSR_ERR_INVALID_ARG, "backward scratch must be 16-byte aligned");
+    const int64_t R = num_rendered;
+    if (P > 0 && R > 0 && (!dL_ddistortion || !saved)) return fail(GSR_ERR_INVALID_ARG, "dL_ddistortion / saved are NULL");
+    if (P == 0) { HIP_OK(hipGetLastError()); return GSR_OK; }
+    GsrBwdScratch w = gsr_carve_bwd((char*)bwd_scratch, P, R);
+    *splat_grads_out = w.splat_grads;
+    if (R == 0) {      // no state to read: zero rows
+        HIP_OK(hipMemsetAsync(w.splat_grads, 0, (size_t)P * 12 * sizeof(float), st));
+        HIP_OK(hipGetLastError());
+        return GSR_OK;
+    }
+    const GsrSavedFrame f = saved_frame(cam, P, R, geom_buffer, binning_buffer, image_buffer);
+    {   StageTimer t(GSR_STAGE_RENDER_BWD, st);
+        gsr_launch_distortion_walk(cam, R, f, g_bwd_heavy_first, dL_ddistortion, saved, depth_mode, w.inst_grads, w.inst_flag, st);
+    }
+    STAGE_CHECK("distortion backward walk");
+    {   StageTimer t(GSR_STAGE_GATHER_BWD, st);
+        gsr_launch_reduce_instances(P, R, f.order, f.offsets, f.splats, w.inst_grads, w.inst_flag, w.splat_grads, w.unit_first, w.unit_piece, st);
+    }
+    STAGE_CHECK("distortion backward reduce");
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 // gsr_backward_preprocess and, with `camera`, gsr_backward_preprocess_camera
 static int backward_preprocess(const GsrRasterSettings* settings, int P, int M, const float* means3D, const float* shs,
                                const float* colors_precomp, const float* opacities, const float* scales,

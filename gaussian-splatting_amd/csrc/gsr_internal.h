@@ -403,6 +403,15 @@ void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R,
 // of a GsrBwdScratch; gsr_launch_reduce_instances on the same stream turns them into the [P,12] rows.  R > 0.
 void gsr_launch_feature_geometry_walks(const GsrCamDev& cam, int64_t R, const GsrSavedFrame& f, int order_mode /*the blend backward's: 0 = index order*/,
                                        const float* features, const float* dL_dout, int C, float* inst_grads, uint32_t* inst_flag, hipStream_t st);
+// distortion.hip: the distortion loss on a saved frame (gsr_distortion / gsr_distortion_backward).  The forward writes every in-band, in-image pixel of
+// distortion[H,W] and, unless NULL, of the two planes of saved[2,H,W], zeros included; _defaults fills the band's rows without reading any state (the
+// call with P == 0 or num_rendered == 0).  The walk clears the flag words of the R instances and leaves the blend backward's instance records (words 0..5
+// and 9; 6, 7, 8, 10, 11 zero) in inst_grads / inst_flag of a GsrBwdScratch for gsr_launch_reduce_instances on the same stream.  R > 0.
+void gsr_launch_distortion(const GsrCamDev& cam, const GsrSavedFrame& f, float* distortion, float* saved /*NULL: not wanted*/, int depth_mode,
+                           hipStream_t st);
+void gsr_launch_distortion_defaults(const GsrCamDev& cam, float* distortion, float* saved, hipStream_t st);
+void gsr_launch_distortion_walk(const GsrCamDev& cam, int64_t R, const GsrSavedFrame& f, int order_mode /*the blend backward's: 0 = index order*/,
+                                const float* dL_ddistortion, const float* saved, int depth_mode, float* inst_grads, uint32_t* inst_flag, hipStream_t st);
 
 // adam.hip
 void gsr_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,

@@ -648,6 +648,94 @@ def render_features(rendered: torch.Tensor, features: torch.Tensor, geometry: bo
     return _RenderFeaturesGeometry.apply(features, means3D, means2D, opacities, scales, rotations, cov3D, frame)
 
 
+def _distortion_forward(frame: _FeatureFrame, depth_mode: int, want_saved: bool, device) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """gsr_distortion on the state a tracking forward left -> (D[H,W], saved[2,H,W] or None), fp32."""
+    lib = _lib.load()
+    rs, fwd = frame.settings, frame.fwd
+    H, W = int(rs.image_height), int(rs.image_width)
+    P = int(frame.means3D.shape[0])
+    out = torch.zeros(H, W, dtype=torch.float32, device=device)      # (with `tile_rows` the library leaves pixels outside the band untouched)
+    saved = torch.zeros(2, H, W, dtype=torch.float32, device=device) if want_saved else None
+    keep: list = []
+    with torch.cuda.device(device):
+        s = _make_settings(rs, keep, frame.tile_rows, bg_image=True)
+        rec = _lib.DistortionOut(out.data_ptr(), saved.data_ptr() if want_saved else None, depth_mode, 0)
+        _lib.check(lib.gsr_distortion(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), C.byref(rec),
+                                      _stream_ptr(device)), "gsr_distortion")
+    return out, saved
+
+
+def _distortion_records(frame: _FeatureFrame, grad_out, saved, depth_mode: int) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """gsr_distortion_backward -> (the [P,12] records, a view into the scratch returned beside it; None for P == 0)."""
+    lib = _lib.load()
+    device = grad_out.device
+    P = int(frame.means3D.shape[0])
+    fwd = frame.fwd
+    keep: list = []
+    s = _make_settings(frame.settings, keep, frame.tile_rows, bg_image=True)
+    scratch = _backward_scratch(lib, P, fwd.num_rendered, device)
+    rec_ptr = C.c_void_p(0)
+    _lib.check(lib.gsr_distortion_backward(C.byref(s), P, fwd.num_rendered, _ptr(fwd.geom), _ptr(fwd.binning), _ptr(fwd.img), _ptr(grad_out),
+                                           _ptr(saved), depth_mode, _ptr(scratch), C.byref(rec_ptr), _stream_ptr(device)),
+               "gsr_distortion_backward")
+    if P == 0:
+        return None, scratch
+    off = int(rec_ptr.value) - scratch.data_ptr()
+    return scratch[off:off + P * 48].view(torch.float32).view(P, 12), scratch
+
+
+class _Distortion(torch.autograd.Function):
+    """D[H,W] of gsr_distortion on a frame's state, differentiable in the caller's own means3D, means2D, opacities, scales, rotations, cov3D_precomp
+    (None where the rasterizer call had none): the backward runs gsr_distortion_backward followed by the per-Gaussian backward
+    (gsr_backward_preprocess).  It keeps its own references to the state (the frame) and the forward's two planes of totals; without a gradient to
+    compute neither is kept nor are the planes allocated.  The camera is a constant on this path."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D, frame: _FeatureFrame, depth_mode: int):
+        device = frame.means3D.device
+        need = any(ctx.needs_input_grad[:6])
+        out, saved = _distortion_forward(frame, depth_mode, need, device)
+        if need:
+            ctx.frame, ctx.saved, ctx.depth_mode = frame, saved, depth_mode
+            ctx.meta = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in (means3D, means2D, opacities, scales, rotations, cov3D))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        frame = ctx.frame
+        device = grad_out.device
+        need = ctx.needs_input_grad
+        g = _f32c(grad_out)
+        out = [None] * 6
+        if int(frame.means3D.shape[0]) > 0:
+            with torch.cuda.device(device):
+                records, _scratch = _distortion_records(frame, g, ctx.saved, ctx.depth_mode)
+                dm2, _, dop, dm3, dcov, _, dsc, drot = _geometry_from_records(frame, records, device)
+            for k, t in enumerate((dm3, dm2, dop, dsc, drot, dcov)):
+                if need[k] and ctx.meta[k] is not None and t is not None:
+                    out[k] = t.view(ctx.meta[k][0]).to(ctx.meta[k][1])
+        else:
+            out = [None if (m is None or not need[k]) else torch.zeros(m[0], dtype=m[1], device=device) for k, m in enumerate(ctx.meta)]
+        return (*out, None, None)
+
+
+def distortion_map(rendered: torch.Tensor, inverse_depth: bool = False) -> torch.Tensor:
+    """-> D[H,W] = sum_i sum_j w_i w_j |t_i - t_j| over the contributors of every pixel of a frame that has ALREADY been rendered: the Mip-NeRF 360
+    distortion loss of 2DGS / GOF / RaDe-GS (no reference counterpart; include/gsr.h gsr_distortion), which keeps the mass of a ray in one place and
+    removes floaters and semi-transparent shells.  w = alpha * T are the frame's blend weights, t the Gaussian's view-space depth z or, with
+    `inverse_depth=True`, 1/z (the bounded choice for unbounded scenes).  NOT normalised: divide by the square of the alpha image of
+    `return_alpha=True` for the normalised form.  `rendered` and the state it is read from are `render_features`'s: any tensor computed from one
+    rasterizer call's outputs with gradients enabled, before that call's `backward()` frees the state (or with `retain_graph=True`); no second
+    forward.  D is differentiable in the tensors that were PASSED TO THE RASTERIZER CALL behind `rendered` -- means3D (its depth included),
+    opacities, scales + rotations or cov3D_precomp, and means2D if it was passed -- which autograd adds to what the colour loss delivers; the camera
+    is a constant on this path.  The backward keeps its own references to the state: it still runs after the frame's own `backward()`.  When no
+    input needs a gradient nothing is kept.  With `tile_rows`, pixels outside the band are 0 and the gradients are the band's.  Two calls give the
+    same bits.  For the depth map itself see `pixel_probe` / the inverse-depth image."""
+    st = _saved_state(rendered, "distortion_map", "distortion")
+    frame, (means3D, means2D, opacities, scales, rotations, cov3D) = _geometry_frame(st)
+    return _Distortion.apply(means3D, means2D, opacities, scales, rotations, cov3D, frame, 1 if inverse_depth else 0)
+
+
 def _mark_visible(points: torch.Tensor, name: str, viewmatrix, projmatrix) -> torch.Tensor:
     """gsr_mark_visible -> bool[P]: in front of the near plane (the reference's checkFrustum with prefiltered = False)."""
     lib = _lib.load()
@@ -1059,6 +1147,20 @@ class GaussianRasterizer(nn.Module):
         c = lambda t: _f32c(t.detach()) if t is not None else None      # noqa: E731  (what the tracking forward read)
         frame = _FeatureFrame(self.raster_settings, tile_rows, fwd, radii, c(means3D), c(opacities), c(scales), c(rotations), c(cov3D_precomp))
         return _RenderFeaturesGeometry.apply(features, means3D, None, opacities, scales, rotations, cov3D_precomp, frame), radii
+
+    def distortion(self, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, inverse_depth: bool = False):
+        """-> (D[H,W], radii[P]): `distortion_map` for this camera without a render of one's own to hand (no reference counterpart): runs a tracking
+        forward with zero colours under no_grad, honours `tile_rows`, then the distortion loss on its state, differentiable in means3D, opacities and
+        scales + rotations / cov3D_precomp."""
+        _lib.load()
+        _require_cuda(means3D, "means3D")
+        device = means3D.device
+        tile_rows = getattr(self, "tile_rows", None)
+        with torch.no_grad(), torch.cuda.device(device):
+            _s, _P, fwd, radii, _keep = self._tracking_forward(means3D, opacities, scales, rotations, cov3D_precomp)
+        c = lambda t: _f32c(t.detach()) if t is not None else None      # noqa: E731  (what the tracking forward read)
+        frame = _FeatureFrame(self.raster_settings, tile_rows, fwd, radii, c(means3D), c(opacities), c(scales), c(rotations), c(cov3D_precomp))
+        return _Distortion.apply(means3D, None, opacities, scales, rotations, cov3D_precomp, frame, 1 if inverse_depth else 0), radii
 
 
 class SparseGaussianAdam(torch.optim.Adam):

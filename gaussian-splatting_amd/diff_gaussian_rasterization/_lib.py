@@ -88,6 +88,11 @@ class PixelProbeOut(C.Structure):
                 ("top_weight", C.c_void_p), ("count", C.c_void_p), ("threshold", C.c_float), ("reserved", C.c_int32)]
 
 
+class DistortionOut(C.Structure):
+    """GsrDistortionOut of include/gsr.h (gsr_distortion)."""
+    _fields_ = [("distortion", C.c_void_p), ("saved", C.c_void_p), ("depth_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AdamTensor(C.Structure):
     """GsrAdamTensor of include/gsr.h (gsr_adam_step_multi)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
@@ -132,6 +137,8 @@ SIGNATURES = {
     "gsr_feature_grad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "gsr_render_features_backward": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 4 + [C.c_int, _vp, _vp, _vp]),
     "gsr_render_features_backward_geometry": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.c_int, _vp, C.POINTER(C.c_void_p), _vp]),
+    "gsr_distortion": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 3 + [C.POINTER(DistortionOut), _vp]),
+    "gsr_distortion_backward": (C.c_int, [_RS, C.c_int, C.c_int32] + [_vp] * 5 + [C.c_int, _vp, C.POINTER(C.c_void_p), _vp]),
     "gsr_preprocess_forward": (C.c_int, [_RS, C.c_int, C.c_int] + [_vp] * 11),
     "gsr_rasterize_from_splats": (C.c_int, [_RS, C.c_int, _vp] + _RECORDS_OUT),
     "gsr_route_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -420,6 +420,57 @@ int gsr_render_features_backward_geometry(const GsrRasterSettings* settings, int
                                           float** splat_grads_out, void* stream);
 
 /*
+ * Distortion loss on a rendered frame (no reference counterpart): the Mip-NeRF 360 regulariser that 2DGS / GOF / RaDe-GS train with,
+ *     D(p) = sum_i sum_j w_i w_j |t_i - t_j|
+ * which is quadratic in the blend weights and so beyond gsr_render_features.  Read from the state of gsr_pixel_probe / gsr_render_features
+ * (a forward run with no_backward == 0, the same settings, the same buffers, num_rendered as returned); the states of the record entry points
+ * (from_splats / from_packed / from_segments) are not supported.  Contributor rule, theirs: the entry is valid (power <= 0, alpha >= 1/255,
+ * alpha capped at 0.99) and its list position is <= n_contrib[p]; n_contrib is the authority on termination; w_i = alpha_i T_i.
+ * t_i is the Gaussian's view-space depth z (depth_mode 0) or 1/z (depth_mode 1, the bounded choice for unbounded scenes): the two values of
+ * the splat record, those of out_invdepth and gsr_pixel_probe (which also deliver the depth maps themselves).
+ * THE CONTRACT is the prefix form in list order -- equal to the pairwise form because t is monotone along a depth-sorted list --: front to
+ * back over the contributors of p, with A_<i = sum_{j<i} w_j and B_<i = sum_{j<i} w_j t_j,
+ *     D(p) = 2 sigma sum_i w_i (t_i A_<i - B_<i)                      sigma = +1 for z, -1 for 1/z
+ * D is NOT normalised (divide by the square of the alpha image for the normalised form).  A pixel with fewer than two contributors has
+ * D = 0 exactly.
+ * `saved` [2,H,W] (may be NULL when no backward follows) is what the backward needs of the forward: plane 0 = sum_i w_i, plane 1 =
+ * sum_i w_i (t_i - c), with c the t of LIST POSITION 0 OF THE PIXEL'S TILE (the first entry of the tile's range, whether or not it
+ * contributes to p).  D and its derivatives are invariant under t -> t - c, and both kernels form every product of a t with a sum of weights
+ * on t - c: t A - B would subtract two numbers of the size of the scene depth to get one of the size of a depth difference.
+ * gsr_distortion_backward: the per-Gaussian [P,12] records of gsr_backward_blend for a loss L(D), g = dL_ddistortion[p], with the suffix
+ * sums A_>i, B_>i:
+ *     u_i = dD/dw_i = 2 sigma [t_i (A_<i - A_>i) - B_<i + B_>i]        v_i = dD/dt_i = 2 sigma w_i (A_<i - A_>i)
+ *     s_i = g u_i
+ *     dL/dalpha_i = T_i s_i - (sum_{j>i} w_j s_j) / (1 - alpha_i)       (gsr_render_features_backward_geometry's line, with this s)
+ *     m_i = opacity_i G_i dL/dalpha_i
+ * words 0..5 exactly as gsr_render_features_backward_geometry defines them from m (px, py, A, B, C, opacity), and
+ *     word 9 = dL/d(1/z_g) = sum_p g v_ip (depth_mode 1),  = -z_g^2 sum_p g v_ip (depth_mode 0);       words 6, 7, 8, 10, 11 = 0
+ * so that gsr_backward_preprocess follows unchanged: its inverse-depth term (dL/dz += -word9 / z^2) delivers the depth path to means3D.
+ * No gradient through culling, radii, tile assignment, depth order or the two cut-offs; the 0.99 cap is passed straight through; the camera
+ * is a constant; no gradient with respect to `saved`.  With a band of tile rows (tile_y0 / tile_y1) the maps are written inside the band
+ * only (every pixel of the band inside the image, zeros included), dL_ddistortion / saved are read inside the band only and the records are
+ * the band's contribution.  P == 0 or num_rendered == 0: zeros over the band / zero rows (P == 0: *splat_grads_out = NULL), and the state
+ * buffers, dL_ddistortion and saved are not read.  Fp32, no atomics, every sum in a fixed order: two runs give the same bits.
+ * `bwd_scratch`: gsr_backward_scratch_bytes(P, num_rendered) bytes, 16-byte aligned; *splat_grads_out points into it.  A NULL `out` or
+ * `distortion`, a depth_mode outside {0, 1}, negative P / num_rendered, NULL state buffers / dL_ddistortion / saved with P > 0 and
+ * num_rendered > 0, a NULL bwd_scratch with P > 0 and a NULL splat_grads_out are GSR_ERR_INVALID_ARG.
+ */
+typedef struct GsrDistortionOut {
+    float*  distortion;     /* [H,W] */
+    float*  saved;          /* [2,H,W] or NULL: (sum w, sum w (t - c)), for gsr_distortion_backward */
+    int32_t depth_mode;     /* 0: t = z, 1: t = 1/z */
+    int32_t reserved;
+} GsrDistortionOut;
+int gsr_distortion(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                   const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                   const GsrDistortionOut* out, void* stream);
+int gsr_distortion_backward(const GsrRasterSettings* settings, int P, int32_t num_rendered,
+                            const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                            const float* dL_ddistortion /* [H,W] */, const float* saved /* [2,H,W], the forward's */, int depth_mode,
+                            void* bwd_scratch /* gsr_backward_scratch_bytes(P, num_rendered) */,
+                            float** splat_grads_out, void* stream);
+
+/*
  * Two-axis sharding (no reference counterpart): the per-Gaussian stages are sharded over the GAUSSIAN
  * axis (every rank owns P/G Gaussians, their parameters and optimizer state), binning + blending over the PIXEL axis
  * (bands of tile rows).  Forward: gsr_preprocess_forward on the own shard -> all-gather of the 64-byte splat records ->
