@@ -59,6 +59,7 @@ UNITS = [
     ("ssim.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("knn.hip", ["-ffp-contract=off"]),
     ("density.hip", ["-ffp-contract=off"]),
+    ("mcmc.hip", ["-ffp-contract=off"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

@@ -1614,6 +1614,26 @@ int gsr_density_stats(int P, const float* viewspace_grad, const uint8_t* visible
     return GSR_OK;
 }
 
+int gsr_mcmc_inject_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
+                          int activated, float noise_scale, float gate_k, float gate_x0, void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!xyz || !scales || !rotations || !opacities || !noise) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_mcmc_noise(P, xyz, scales, rotations, opacities, noise, activated != 0, noise_scale, gate_k, gate_x0, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_relocation(int n, const float* opacities, const float* scales, const int32_t* ratios, float* new_opacities, float* new_scales,
+                        void* stream) {
+    if (n < 0) return fail(GSR_ERR_INVALID_ARG, "n < 0");
+    if (n == 0) return GSR_OK;
+    if (!opacities || !scales || !ratios || !new_opacities || !new_scales) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_mcmc_relocation(n, opacities, scales, ratios, new_opacities, new_scales, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

@@ -432,6 +432,12 @@ void gsr_launch_sparse_adam(float* p, const float* g, float* m, float* v, const 
 // density.hip: per-iteration density-control statistics
 void gsr_launch_density_stats(int P, const float* grad, const uint8_t* visible, const int32_t* radii, float* accum, float* denom,
                               float* max_radii, hipStream_t st);
+// mcmc.hip: 3DGS-MCMC density control -- the per-iteration noise on the means (in place; rows whose displacement is not finite are left alone)
+// and the opacity / scale correction of relocated Gaussians (fp64 inside)
+void gsr_launch_mcmc_noise(int P, float* xyz, const float* scales, const float* rot, const float* opac, const float* noise, int activated,
+                           float noise_scale, float gate_k, float gate_x0, hipStream_t st);
+void gsr_launch_mcmc_relocation(int n, const float* opac, const float* scales, const int32_t* ratios, float* new_opac, float* new_scales,
+                                hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

@@ -154,6 +154,8 @@ SIGNATURES = {
     "gsr_sparse_adam_step": (C.c_int, [_vp] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "gsr_sparse_adam_step_multi": (C.c_int, [C.POINTER(SparseAdamTensor), C.c_int32, _vp, C.c_int64, C.c_double, C.c_double, _vp]),
     "gsr_density_stats": (C.c_int, [C.c_int] + [_vp] * 7),
+    "gsr_mcmc_inject_noise": (C.c_int, [C.c_int] + [_vp] * 5 + [C.c_int, C.c_float, C.c_float, C.c_float, _vp]),
+    "gsr_mcmc_relocation": (C.c_int, [C.c_int] + [_vp] * 5 + [_vp]),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

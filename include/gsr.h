@@ -636,6 +636,32 @@ int gsr_density_stats(int P, const float* viewspace_grad, const uint8_t* visible
                       float* denom, float* max_radii2D, void* stream);
 
 /*
+ * 3DGS-MCMC density control (Kheradmand et al. 2024; gsplat's MCMCStrategy): the two native pieces.  gsr_scene/mcmc.py holds the
+ * sampling and the optimizer bookkeeping around them.  (Additive, the ABI version stays 4.)
+ *
+ * Noise on the means, once per training iteration after the optimizer step, in place, one streaming pass:
+ *   s = activated ? scales[i] : exp(scales[i]);   o = activated ? opacities[i] : sigmoid(opacities[i]);   q = rotations[i] / |rotations[i]|
+ *   g = 1 / (1 + exp(-gate_k ((1 - o) - gate_x0)))                         (upstream: gate_k 100, gate_x0 0.995; evaluated in fp64)
+ *   d = R(q) diag(s^2) R(q)^T noise[i] * g * noise_scale;                  xyz[i] += d
+ * xyz, scales, noise are [P,3]; rotations [P,4] (w, x, y, z; the rasterizer's convention); opacities [P]; noise is standard-normal and comes
+ * from the caller (no generator in the library); noise_scale is upstream's noise_lr * xyz_lr.  A row whose d is not finite in all three
+ * components -- a NaN / inf scale, a zero quaternion, a NaN opacity, a non-finite noise value -- keeps its xyz bit for bit.  Pointers that are
+ * all 16-byte aligned take 16-byte accesses (four Gaussians per lane); any other alignment is accepted and computes the same values.
+ */
+int gsr_mcmc_inject_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
+                          int activated, float noise_scale, float gate_k, float gate_x0, void* stream);
+/*
+ * Opacity and scale of a Gaussian that is replaced by N = clamp(ratios[i], 1, 51) copies of itself so that the rendered image is unchanged
+ * (upstream's `compute_relocation`), on ACTIVATED opacities [n] and scales [n,3], evaluated in fp64 and rounded once:
+ *   new_opacities[i] = 1 - (1 - o)^(1/N)  (as -expm1(log1p(-o) / N));
+ *   new_scales[i]    = scales[i] o / D,   D = sum_{k=0}^{N-1} (-1)^k C(N, k+1) new_o^(k+1) / sqrt(k+1)
+ * (upstream's double sum over a binomial table, collapsed by the hockey-stick identity).  o == 0: opacity 0, scale unchanged.  o outside
+ * [0, 1) or not finite: both outputs are the inputs.  Clamping to a minimum opacity and the inverse activations are the caller's.
+ */
+int gsr_mcmc_relocation(int n, const float* opacities, const float* scales, const int32_t* ratios, float* new_opacities, float* new_scales,
+                        void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points
