@@ -10,6 +10,8 @@ Translation units and their flags:
   features.hip, feature_geom.hip,
   distortion.hip                       (FMA contraction allowed; image tolerance 1e-5; what they must compute identically -- box
                                         test, exponent / alpha -- is csrc/gsr_blend.h, their wave reductions csrc/gsr_wave.h)
+  bilagrid.hip     -ffp-contract=fast -fno-slp-vectorize   (the image kernels' flags: the trilinear blend is 96 multiply-adds per pixel, tolerance
+                                        1e-5; the pixel -> cell map is products only, nothing in it contracts; total variation is fp64)
   gsr_api.cpp                          (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
@@ -60,6 +62,7 @@ UNITS = [
     ("knn.hip", ["-ffp-contract=off"]),
     ("density.hip", ["-ffp-contract=off"]),
     ("mcmc.hip", ["-ffp-contract=off"]),
+    ("bilagrid.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

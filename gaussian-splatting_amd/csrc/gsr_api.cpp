@@ -1634,6 +1634,80 @@ int gsr_mcmc_relocation(int n, const float* opacities, const float* scales, cons
     return GSR_OK;
 }
 
+// ---- bilateral grid (bilagrid.hip) ----
+static int bilagrid_grid_ok(int L, int Gh, int Gw) {
+    if (L < 2 || Gh < 2 || Gw < 2 || L > GSR_BILAGRID_MAX || Gh > GSR_BILAGRID_MAX || Gw > GSR_BILAGRID_MAX)
+        return fail(GSR_ERR_UNSUPPORTED, "bilateral grid: L, Gh, Gw must be 2..64, got " + std::to_string(L) + " x " + std::to_string(Gh) + " x " +
+                                             std::to_string(Gw));
+    return GSR_OK;
+}
+
+static int bilagrid_plan_checked(int H, int W, int L, int Gh, int Gw, GsrBilagridPlan* p) {
+    if (H < 1 || W < 1) return fail(GSR_ERR_INVALID_ARG, "bilateral grid: image size must be positive, got " + std::to_string(H) + " x " + std::to_string(W));
+    if (H > GSR_BILAGRID_MAX_IMAGE || W > GSR_BILAGRID_MAX_IMAGE) return fail(GSR_ERR_UNSUPPORTED, "bilateral grid: image side above 2^23 pixels");
+    if (int rc = bilagrid_grid_ok(L, Gh, Gw)) return rc;
+    gsr_bilagrid_plan(H, W, L, Gh, Gw, p);
+    if ((int64_t)p->ncells * p->maxchunks > 0x7FFFFFFFll) return fail(GSR_ERR_UNSUPPORTED, "bilateral grid: more than 2^31-1 workgroups");
+    return GSR_OK;
+}
+
+size_t gsr_bilagrid_scratch_bytes(int H, int W, int L, int Gh, int Gw) {
+    GsrBilagridPlan p;
+    if (bilagrid_plan_checked(H, W, L, Gh, Gw, &p) != GSR_OK) return 0;
+    return gsr_bilagrid_scratch_floats(p) * sizeof(float);
+}
+
+int gsr_bilagrid_slice(int H, int W, int L, int Gh, int Gw, const float* grid, const float* image, float* out, void* stream) {
+    GsrBilagridPlan p;
+    if (int rc = bilagrid_plan_checked(H, W, L, Gh, Gw, &p)) return rc;
+    if (!grid || !image || !out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_bilagrid_slice(p, grid, image, out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilagrid_slice_backward(int H, int W, int L, int Gh, int Gw, const float* grid, const float* image, const float* dL_dout,
+                                float* dL_dgrid, float* dL_dimage, void* scratch, size_t scratch_bytes, void* stream) {
+    GsrBilagridPlan p;
+    if (int rc = bilagrid_plan_checked(H, W, L, Gh, Gw, &p)) return rc;
+    if (!grid || !image || !dL_dout || !dL_dgrid || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only dL_dimage may be NULL)");
+    const size_t need = gsr_bilagrid_scratch_floats(p) * sizeof(float);
+    if (scratch_bytes < need)
+        return fail(GSR_ERR_INVALID_ARG, "bilateral grid: scratch of " + std::to_string(scratch_bytes) + " bytes, gsr_bilagrid_scratch_bytes asks for " +
+                                             std::to_string(need));
+    if ((uintptr_t)scratch & 3) return fail(GSR_ERR_INVALID_ARG, "bilateral grid: scratch must be 4-byte aligned");
+    gsr_launch_bilagrid_slice_backward(p, grid, image, dL_dout, dL_dgrid, dL_dimage, (float*)scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+static int bilagrid_tv_ok(int N, int L, int Gh, int Gw) {
+    if (N < 1) return fail(GSR_ERR_INVALID_ARG, "bilateral grid: N must be positive, got " + std::to_string(N));
+    return bilagrid_grid_ok(L, Gh, Gw);
+}
+
+int64_t gsr_bilagrid_tv_partial_count(int N, int L, int Gh, int Gw) {
+    if (bilagrid_tv_ok(N, L, Gh, Gw) != GSR_OK) return 0;
+    return gsr_bilagrid_tv_partial_count_impl(N, L, Gh, Gw);
+}
+
+int gsr_bilagrid_tv(int N, int L, int Gh, int Gw, const float* grids, double* partials, float* tv_out, void* stream) {
+    if (int rc = bilagrid_tv_ok(N, L, Gh, Gw)) return rc;
+    if (!grids || !partials || !tv_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)partials & 7) return fail(GSR_ERR_INVALID_ARG, "bilateral grid: partials must be 8-byte aligned");
+    gsr_launch_bilagrid_tv(N, L, Gh, Gw, grids, partials, tv_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, const float* dL_dtv, float* dL_dgrids, void* stream) {
+    if (int rc = bilagrid_tv_ok(N, L, Gh, Gw)) return rc;
+    if (!grids || !dL_dtv || !dL_dgrids) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_bilagrid_tv_backward(N, L, Gh, Gw, grids, dL_dtv, dL_dgrids, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

@@ -438,6 +438,26 @@ void gsr_launch_mcmc_noise(int P, float* xyz, const float* scales, const float* 
                            float noise_scale, float gate_k, float gate_x0, hipStream_t st);
 void gsr_launch_mcmc_relocation(int n, const float* opac, const float* scales, const int32_t* ratios, float* new_opac, float* new_scales,
                                 hipStream_t st);
+// bilagrid.hip: bilateral-grid appearance model.  The plan is the one place that maps pixels to xy cells and cells to workgroups:
+// the host sizes the scratch with it and the kernels take it by value.
+#define GSR_BILAGRID_MAX 64             // largest grid size per axis (the kernels' LDS is sized for it)
+#define GSR_BILAGRID_MAX_IMAGE (1 << 23)
+struct GsrBilagridAxis { float gm1, inv; int n, size; };      // grid points - 1, 1 / pixels (both as the fp32 factors of the coordinate), grid points, pixels
+struct GsrBilagridPlan {
+    GsrBilagridAxis ax, ay;
+    int L;
+    int twl, tw, steps, th;             // tile: tw = 2^twl columns, th = steps * 4 * (64 / tw) rows
+    int maxchunks, ncells;              // tile slots per cell (the largest cell's tiles), (Gw - 1) (Gh - 1)
+};
+void gsr_bilagrid_plan(int H, int W, int L, int Gh, int Gw, GsrBilagridPlan* out);
+static inline size_t gsr_bilagrid_scratch_floats(const GsrBilagridPlan& p) { return (size_t)p.ncells * p.maxchunks * 48 * p.L; }
+void gsr_launch_bilagrid_slice(const GsrBilagridPlan& p, const float* grid, const float* image, float* out, hipStream_t st);
+// dL_dimage may be NULL; scratch: gsr_bilagrid_scratch_floats(p) floats; every element of dL_dgrid is written
+void gsr_launch_bilagrid_slice_backward(const GsrBilagridPlan& p, const float* grid, const float* image, const float* dL_dout, float* dL_dgrid,
+                                        float* dL_dimage, float* scratch, hipStream_t st);
+int64_t gsr_bilagrid_tv_partial_count_impl(int N, int L, int Gh, int Gw);
+void gsr_launch_bilagrid_tv(int N, int L, int Gh, int Gw, const float* grids, double* partials, float* tv_out, hipStream_t st);
+void gsr_launch_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, const float* dL_dtv, float* dL_dgrids, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

@@ -156,6 +156,12 @@ SIGNATURES = {
     "gsr_density_stats": (C.c_int, [C.c_int] + [_vp] * 7),
     "gsr_mcmc_inject_noise": (C.c_int, [C.c_int] + [_vp] * 5 + [C.c_int, C.c_float, C.c_float, C.c_float, _vp]),
     "gsr_mcmc_relocation": (C.c_int, [C.c_int] + [_vp] * 5 + [_vp]),
+    "gsr_bilagrid_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "gsr_bilagrid_slice": (C.c_int, [C.c_int] * 5 + [_vp] * 4),
+    "gsr_bilagrid_slice_backward": (C.c_int, [C.c_int] * 5 + [_vp] * 6 + [C.c_size_t, _vp]),
+    "gsr_bilagrid_tv_partial_count": (C.c_int64, [C.c_int] * 4),
+    "gsr_bilagrid_tv": (C.c_int, [C.c_int] * 4 + [_vp] * 4),
+    "gsr_bilagrid_tv_backward": (C.c_int, [C.c_int] * 4 + [_vp] * 4),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

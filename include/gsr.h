@@ -662,6 +662,42 @@ int gsr_mcmc_relocation(int n, const float* opacities, const float* scales, cons
                         void* stream);
 
 /*
+ * Bilateral-grid appearance model ("Bilateral Guided Radiance Field Processing"; gsplat's lib_bilagrid / fused_bilagrid): per-image colour
+ * compensation by a low-resolution grid of 3x4 affine maps, sliced at (pixel position, pixel luminance).  (Additive, the ABI version stays 4.)
+ *
+ * A grid is A[12, L, Gh, Gw] fp32: channel 4 i + j is entry (i, j) of the map, i the output colour, j indexing (r, g, b, 1).  Images are planar
+ * [3, H, W] fp32; values outside [0, 1] are expected.  For pixel (x, y) with colour (r, g, b):
+ *   fx = (x + 0.5) / W (Gw - 1);   fy = (y + 0.5) / H (Gh - 1);   fz = (0.299 r + 0.587 g + 0.114 b) (L - 1), clamped to [0, L - 1]
+ *   cell i0 = min(floor(f), n - 2), fraction t = f - i0 per axis;  A(p) = the trilinear blend of the 8 corners
+ *   out_i = sum_{j<3} A_ij(p) rgb_j + A_i3(p)
+ * (torch's grid_sample with align_corners=True and border padding).  Gradients go to the grid and to the image; the image gradient is the direct
+ * term sum_i dL/dout_i A_ij plus the guidance term w_j (L - 1) sum_i dL/dout_i sum_j' dA_ij'/dfz [rgb, 1]_j', w = (0.299, 0.587, 0.114), where
+ * dA/dfz is the slope of cell i0 when the UNCLAMPED fz lies in [0, L - 1] (at fz == L - 1 exactly: the slope of the last cell) and 0 outside.
+ * Sizes: 2 <= L, Gh, Gw <= 64; H, W >= 1 (an image may be smaller than the grid).  Anything else is refused before any launch.
+ *
+ * Non-finite pixels: indices are taken from the clamped guidance value and a NaN guidance lands in cell 0, so nothing outside the buffers is
+ * read or written.  That pixel's outputs and image gradient may be non-finite, and so may the grid gradient of the vertices it touches; every
+ * other pixel's output and image gradient keeps its value bit for bit.
+ *
+ * The backward uses no floating-point atomics: per-workgroup partial sums in `scratch` (gsr_bilagrid_scratch_bytes bytes, 4-byte aligned; a
+ * smaller scratch_bytes is refused) are added in a fixed order, so two runs give the same bits.  dL_dimage may be NULL; dL_dgrid is the same
+ * bits either way, and every element of it is written.
+ */
+size_t gsr_bilagrid_scratch_bytes(int H, int W, int L, int Gh, int Gw);      /* 0: unsupported sizes */
+int gsr_bilagrid_slice(int H, int W, int L, int Gh, int Gw, const float* grid, const float* image, float* out, void* stream);
+int gsr_bilagrid_slice_backward(int H, int W, int L, int Gh, int Gw, const float* grid, const float* image, const float* dL_dout,
+                                float* dL_dgrid, float* dL_dimage, void* scratch, size_t scratch_bytes, void* stream);
+/*
+ * Total variation of a set of grids X[N, 12, L, Gh, Gw]:
+ *   tv = (1 / N) sum_{axis in L, Gh, Gw} sum (X[.. k + 1 ..] - X[.. k ..])^2 / count_axis,   count_axis = 12 (n_axis - 1) (the other two sizes)
+ * evaluated in fp64 and rounded once.  The forward writes one fp64 partial sum per workgroup into `partials` (gsr_bilagrid_tv_partial_count
+ * doubles, 8-byte aligned) and their sum, added in index order, into tv_out[1]; the backward takes dL/dtv as ONE device scalar.
+ */
+int64_t gsr_bilagrid_tv_partial_count(int N, int L, int Gh, int Gw);          /* 0: unsupported sizes */
+int gsr_bilagrid_tv(int N, int L, int Gh, int Gw, const float* grids, double* partials, float* tv_out, void* stream);
+int gsr_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, const float* dL_dtv, float* dL_dgrids, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points

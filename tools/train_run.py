@@ -15,6 +15,7 @@ What is mirrored from the reference (train.py:73-190, arguments/__init__.py:72-1
   * density statistics every iteration and clone / split / prune every 100 iterations from 500 to 15 000 with gradient
     threshold 0.0002, opacity floor 0.005, screen-size pruning after iteration 3000, opacity reset every 3000 iterations
     (train.py:160-174, arguments/__init__.py:91-95).
+Beyond the reference, off by default: `--bilateral_grid`, gsplat's per-image appearance compensation (fused_bilagrid).
 Reported: iterations/s (whole run and per 5000-iteration window), the Gaussian count over time, peak device memory, the
 largest R-sized scratch buffers.  One JSON line on stdout (also written to gpurun_out/train_run.json)."""
 from __future__ import annotations
@@ -62,6 +63,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--grad-threshold", type=float, default=0.0002, help="densify_grad_threshold (arguments/__init__.py:95)")
     ap.add_argument("--tag", default="")
+    ap.add_argument("--bilateral_grid", action="store_true",
+                    help="per-camera appearance compensation (fused_bilagrid.BilateralGrid, 16 x 16 x 8): the rendered image is sliced through its "
+                         "camera's grid before the loss, 10 tv_loss is added, the grids have their own gsr_optim.FusedAdam (lr 2e-3)")
     ap.add_argument("--fuse-sh-step", action="store_true",
                     help="opt-in: the optimizer step of f_dc / f_rest is applied by the per-Gaussian backward kernel "
                          "(diff_gaussian_rasterization.fuse_sh_adam_into_backward); switched off on the iterations that densify, "
@@ -158,6 +162,11 @@ def main():
         stats = DensifyStats.zeros(params["xyz"].shape[0], dev)
         deg, it0 = int(st_["deg"]), int(st_["it"]) + 1
         del st_
+    bil = bil_opt = None
+    if a.bilateral_grid:
+        from fused_bilagrid import BilateralGrid
+        bil = BilateralGrid(len(cams)).to(dev)
+        bil_opt = FusedAdam([bil.grids], lr=2e-3, eps=1e-15)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     t_start = t_win = time.perf_counter()
@@ -179,7 +188,10 @@ def main():
             means3D=params["xyz"], means2D=m2, dc=params["f_dc"], shs=params["f_rest"], opacities=torch.sigmoid(params["opacity"]),
             scales=torch.exp(params["scaling"]), rotations=torch.nn.functional.normalize(params["rotation"]))
         gt = gts[ci]
-        loss = fused_train_loss(img, gt, 0.2)          # train.py:119-126 as one fused kernel pair (L1 + SSIM + mix)
+        if bil is not None:
+            loss = fused_train_loss(bil(img, ci), gt, 0.2) + 10.0 * bil.tv_loss()
+        else:
+            loss = fused_train_loss(img, gt, 0.2)          # train.py:119-126 as one fused kernel pair (L1 + SSIM + mix)
         loss.backward()
         with torch.no_grad():
             if it < 15000:
@@ -196,6 +208,9 @@ def main():
                 else:
                     opt.step(radii > 0, radii.shape[0])
                 opt.zero_grad(set_to_none=True)
+                if bil_opt is not None:
+                    bil_opt.step()
+                    bil_opt.zero_grad(set_to_none=True)
         if it % 5000 == 0 or it == a.iters:
             torch.cuda.synchronize()
             now = time.perf_counter()
@@ -312,7 +327,8 @@ def main():
            "value": round(n_run / max(total, 1e-9), 2), "unit": "it/s", "iterations": n_run, "first_iteration": it0, "seconds": round(total, 2), "timeline": timeline,
            "config": {"workload": f"configs[2] stand-in: P0 {P0} -> densified, {W}x{H}, {len(cams)} synthetic views cycled without "
                                   f"replacement, target scene {a.P_target} Gaussians (SURVEY 8(d) generator, seed {a.seed})",
-                      "optimizer": ("FusedAdam (dense)" if a.dense_adam else "SparseGaussianAdam + separate_sh call form") + (" + SH step inside backward (opt-in fusion)" if a.fuse_sh_step else ""),
+                      "optimizer": ("FusedAdam (dense)" if a.dense_adam else "SparseGaussianAdam + separate_sh call form") + (" + SH step inside backward (opt-in fusion)" if a.fuse_sh_step else "")
+                                   + (" + per-camera bilateral grids 16x16x8 (slice before the loss, 10 tv_loss, FusedAdam lr 2e-3)" if a.bilateral_grid else ""),
                       "schedule": f"densify 500..15000 every 100 (grad {a.grad_threshold:g}, opacity 0.005, size 20 after 3000), opacity reset / 3000, "
                                   "SH degree +1 / 1000, position lr 1.6e-4 -> 1.6e-6 x extent", "extent": ext},
            "final_P": int(params["xyz"].shape[0]), "max_P": max(sizes + [P0]), "P_every_1000_iters": sizes,
