@@ -535,6 +535,9 @@ ds_scatter(int P, int nblocks, const uint32_t* __restrict__ keys, const uint16_t
         const int64_t idx = wave_base + r * 64 + lane;
         const bool valid = idx < P;
         const uint32_t d = dig[r];
+        // (the width is a constant and the compiler unrolls the chain already.  match_digit<GSR_DS_BITS> and the v_mbcnt rank take 14 % of the kernel's
+        // VALU instructions away and nothing off its time -- 15.24 -> 15.12 us inside a p10-p90 spread of 0.7, profiles/ab_ranking_widths.json: two waves
+        // per SIMD wait on LDS round trips here, not on issue slots -- so the kernel keeps this form)
         const uint64_t mask = match_digit(d, GSR_DS_BITS, __ballot(valid));
         const uint32_t prior = valid ? (uint32_t)wave_cnt[w][d] : 0u;
         rank[r] = prior + (uint32_t)__popcll(mask & lt_mask);
@@ -619,8 +622,33 @@ __device__ __forceinline__ uint32_t seg_excl_scan(uint32_t v, uint32_t* wsum, in
 // count (LDS atomics on the wave's own table) -> scan over (bin, wave) -> rank with ballot matching against running counts.
 // CntT: uint16_t for segments that fit the LDS buffers (counts and offsets < 65536; two bins share a 32-bit atomic),
 // uint32_t for the oversized ones.
+// One ranking sweep of a pass over the wave's items [wbeg, wend) for a digit width known at compile time (match_digit<BITS>; the rank among the
+// lower lanes by v_mbcnt).  The same stores in the same order as the run-time-width loop of seg_sort.
+template <int BITS, class Mem, typename CntT>
+__device__ __forceinline__ void seg_rank_sweep(const Mem& m, int cur, uint32_t wbeg, uint32_t wend, int sh, CntT* cnt /*the wave's table*/, int lane, uint64_t lt_mask) {
+    constexpr uint32_t dmask = (1u << BITS) - 1u;
+#pragma unroll 1
+    for (uint32_t i0 = wbeg; i0 < wend; i0 += 64u) {      // wave-uniform trips
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool valid = i < wend;
+        uint32_t k = 0, v = 0;
+        if (valid) m.load(cur, i, k, v);
+        const uint32_t d = (k >> sh) & dmask;
+        const uint64_t mask = match_digit<BITS>(d, __ballot(valid));
+        const uint32_t prior = valid ? (uint32_t)cnt[d] : 0u;
+        const uint32_t below = lanes_below(mask, lt_mask);
+        if (valid) {
+            m.store(cur ^ 1, prior + below, k, v);
+            if (below == 0u) cnt[d] = (CntT)(prior + (uint32_t)__popcll(mask));
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// full9: the passes of DS_PASS_BITS and DS_PASS_BITS - 1 bits run seg_rank_sweep (the segments that fit the LDS; false: every pass takes the
+// run-time-width loop below)
 template <class Mem, typename CntT>
-__device__ __forceinline__ int seg_sort(const Mem& m, uint32_t n, int nbits, CntT (*wave_cnt)[DS_PASS_BINS], uint32_t* wsum) {
+__device__ __forceinline__ int seg_sort(const Mem& m, uint32_t n, int nbits, CntT (*wave_cnt)[DS_PASS_BINS], uint32_t* wsum, bool full9 = false) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int cur = 0;
     if (nbits <= 0) return cur;
@@ -655,6 +683,11 @@ __device__ __forceinline__ int seg_sort(const Mem& m, uint32_t n, int nbits, Cnt
             for (int k = 0; k < SG_WAVES; ++k) { wave_cnt[k][tid] = (CntT)run; run += c[k]; }
         }
         __syncthreads();
+        if (full9 && bits == DS_PASS_BITS) {
+            seg_rank_sweep<DS_PASS_BITS>(m, cur, wbeg, wend, sh, wave_cnt[w], lane, lt_mask);
+        } else if (full9 && bits == DS_PASS_BITS - 1) {      // (18 key bits -> 9 + 9, 17 -> 9 + 8: the two shapes of a segment of a few buckets)
+            seg_rank_sweep<DS_PASS_BITS - 1>(m, cur, wbeg, wend, sh, wave_cnt[w], lane, lt_mask);
+        } else {
 #pragma unroll 1
         for (uint32_t i0 = wbeg; i0 < wend; i0 += 64u) {      // wave-uniform trips
             const uint32_t i = i0 + (uint32_t)lane;
@@ -669,6 +702,7 @@ __device__ __forceinline__ int seg_sort(const Mem& m, uint32_t n, int nbits, Cnt
                 if ((mask & lt_mask) == 0ull) wave_cnt[w][d] = (CntT)(prior + (uint32_t)__popcll(mask));
             }
             __builtin_amdgcn_wave_barrier();
+        }
         }
         __syncthreads();
         cur ^= 1;
@@ -744,6 +778,7 @@ struct SegLdsMem {
     uint16_t (*wave_cnt)[DS_PASS_BINS];
     uint32_t* wsum;
     uint32_t (*s_wt)[SG_WAVES];
+    bool full9;      // seg_sort: compile-time-width sweeps (off: option ranking_generic)
 };
 __device__ __forceinline__ uint32_t seg_sort_in_lds(const SegLdsMem& L, const uint2* __restrict__ pairs0, uint32_t begin, uint32_t n, uint32_t base_key, int nbits,
                                                     uint32_t tile_base, const uint2* __restrict__ rect, uint32_t* __restrict__ order, uint2* __restrict__ rect_sorted,
@@ -767,7 +802,7 @@ __device__ __forceinline__ uint32_t seg_sort_in_lds(const SegLdsMem& L, const ui
         }
     }
     __syncthreads();
-    const int cur = seg_sort<SegLds, uint16_t>(m, n, nbits, L.wave_cnt, L.wsum);
+    const int cur = seg_sort<SegLds, uint16_t>(m, n, nbits, L.wave_cnt, L.wsum, L.full9);
     uint32_t ix[SG_OUT], id[SG_OUT];
 #pragma unroll
     for (int j = 0; j < SG_OUT; ++j) {
@@ -787,7 +822,7 @@ __global__ void __launch_bounds__(SG_THREADS)
 ds_segsort(const uint32_t* __restrict__ plan, const uint32_t* __restrict__ frame, const uint32_t* __restrict__ cnt_total, const uint32_t* __restrict__ cnt_tab,
            const uint32_t* __restrict__ tile_tab, int nblocks, uint2* pairs0, uint2* pairs1,
            const uint2* __restrict__ rect, uint32_t* __restrict__ order, uint2* __restrict__ rect_sorted, uint32_t* __restrict__ offsets,
-           uint2* __restrict__ block_first, uint32_t bf_cap, uint32_t* slow_word /*mapped host word or NULL*/) {
+           uint2* __restrict__ block_first, uint32_t bf_cap, uint32_t* slow_word /*mapped host word or NULL*/, int ranking_generic) {
     __shared__ uint32_t s_key[2][DS_CAP];                       // 32 KB (a bucket beyond the LDS capacity: the 32-bit count table instead)
     __shared__ uint16_t s_idx[2][DS_CAP];                       // 16 KB
     __shared__ uint16_t wave_cnt[SG_WAVES][DS_PASS_BINS];       //  8 KB
@@ -863,7 +898,7 @@ ds_segsort(const uint32_t* __restrict__ plan, const uint32_t* __restrict__ frame
     // (the segments tile [0, listed): exactly one ends at `listed`.  Its end BUCKET need not be 2047 -- behind the last
     // non-empty bucket come empty ones that start at `listed` too -- so the element count decides, not the bucket)
     const uint32_t last_listed = end == listed ? end - 1u : 0xFFFFFFFFu;
-    const SegLdsMem L{s_key, s_idx, wave_cnt, wsum, s_wt};
+    const SegLdsMem L{s_key, s_idx, wave_cnt, wsum, s_wt, ranking_generic == 0};
     if (n <= (uint32_t)DS_CAP) {
         seg_sort_in_lds(L, pairs0, begin, n, base_key, nbits, tile_base, rect, order, rect_sorted, offsets, block_first, bf_cap, last_listed, r_ok);
         return;
@@ -978,5 +1013,5 @@ void gsr_launch_depth_bucket_sort(int P, const uint32_t* keys, const uint32_t* t
     hipLaunchKernelGGL(ds_scatter, dim3(nblocks + 1), dim3(S3_THREADS), 0, st, P, nblocks, keys, b.bucket_of, frame, b.eq_tab, b.cnt_tab, b.cnt_total,
                        b.tile_total, b.pairs[0], order, offsets, rect_sorted, b.plan, nseg_cap);
     hipLaunchKernelGGL(ds_segsort, dim3(nseg_cap), dim3(SG_THREADS), 0, st, b.plan, frame, b.cnt_total, b.cnt_tab, b.tile_tab, nblocks, b.pairs[0], b.pairs[1], rect, order,
-                       rect_sorted, offsets, block_first, block_first_cap, slow_word);
+                       rect_sorted, offsets, block_first, block_first_cap, slow_word, g_ranking_generic);
 }

@@ -444,6 +444,18 @@ int gsr_set_option(const char* name, int value) {
         g_bwd_heavy_first = value;
         return GSR_OK;
     }
+    if (!strcmp(name, "ranking_generic")) {
+        if (value != 0 && value != 1) return fail(GSR_ERR_INVALID_ARG, "ranking_generic must be 0 (ranking kernels compiled for the frame's digit widths) or 1 (always the run-time-width ones)");
+        gsr_set_ranking_generic(value);
+        return GSR_OK;
+    }
+    if (!strcmp(name, "debug_last_ranking_widths")) {      // test hook, changes nothing: succeeds iff the most recent emit_scatter / bucket_scatter launches were
+        // instantiated for the bucket digit value >> 4 and the low digit value & 15 (0: the run-time-width kernel)
+        if (value < 0 || value > 0x88) return fail(GSR_ERR_INVALID_ARG, "debug_last_ranking_widths: hb << 4 | lb, each 0 (generic) or 5..8");
+        if (g_ranking_last_hb != (value >> 4) || g_ranking_last_lb != (value & 15))
+            return fail(GSR_ERR_INVALID_ARG, "the last tile sort ran emit_scatter<" + std::to_string(g_ranking_last_hb) + "> and bucket_scatter<" + std::to_string(g_ranking_last_lb) + ">");
+        return GSR_OK;
+    }
     if (!strcmp(name, "level2_scan_mode")) {
         if (value < 0 || value > 2) return fail(GSR_ERR_INVALID_ARG, "level2_scan_mode must be 0 (automatic), 1 (separate scan launch) or 2 (scan folded into the scatter)");
         gsr_set_level2_scan_mode(value);

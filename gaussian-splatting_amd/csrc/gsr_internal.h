@@ -262,6 +262,12 @@ void gsr_launch_tile_sort_level2(const GsrTileSortPlan& plan, int64_t R, int n_t
                                  const uint32_t* bucket_base, const uint32_t* blk2_start, uint32_t* hist2, uint32_t* tile_base,
                                  uint2* ranges, hipStream_t st, int h0 = 0, int h1 = 0 /*level-1 buckets [h0, h1) of a band; (0, 0) = all*/);
 void gsr_set_level2_scan_mode(int v);      // tilesort.hip (option level2_scan_mode)
+// option ranking_generic: 1 = the ranking kernels of tilesort.hip and depthsort.hip in their run-time-digit-width forms only (A/B, tests; ds_scatter has one form).  Defined here
+// (C++17 inline variable): either file is also compiled on its own (tests/simt).
+inline int g_ranking_generic = 0;
+inline void gsr_set_ranking_generic(int v) { g_ranking_generic = v; }
+// TEST HOOK (option debug_last_ranking_widths): the digit widths the most recent emit_scatter / bucket_scatter launches were instantiated for (0: generic, -1: none yet)
+inline int g_ranking_last_hb = -1, g_ranking_last_lb = -1;
 // sort.hip: in-place exclusive scan of every digit row of a [ndigits][nblocks] block-histogram table + row totals
 void gsr_launch_rs_scan(uint32_t* block_hist, int nblocks, int ndigits, uint32_t* digit_total, hipStream_t st);
 void gsr_launch_ranges(int64_t R, int n_tiles, const void* sorted_keys, bool key16, uint2* ranges, bool already_zeroed,

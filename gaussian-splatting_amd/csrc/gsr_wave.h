@@ -69,6 +69,25 @@ __device__ __forceinline__ uint32_t div_small(uint32_t a, uint32_t b, uint32_t& 
     return q;
 }
 
+// a * b for a, b < 2^24: v_mul_u32_u24, one issue slot, where the full v_mul_lo_u32 takes four.  The low 32 bits of the product, i.e. exactly
+// `a * b` while both operands fit 24 bits (the caller's duty; the host form masks the operands as the instruction does, so a violation shows in tests/simt).
+__device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) {
+#ifdef GSR_SIMT_SHIM
+    return (a & 0xFFFFFFu) * (b & 0xFFFFFFu);
+#else
+    return __umul24(a, b);
+#endif
+}
+// div_small for operands that also keep q * b inside 24 x 24 bits (q <= 2^16, b < 2^16): the same quotient and remainder, the product by mul_u24
+__device__ __forceinline__ uint32_t div_small24(uint32_t a, uint32_t b, uint32_t& rem) {
+    uint32_t q = (uint32_t)((float)a * __builtin_amdgcn_rcpf((float)b));
+    int r = (int)a - (int)mul_u24(q, b);
+    if (r < 0) { --q; r += (int)b; }
+    else if (r >= (int)b) { ++q; r -= (int)b; }
+    rem = (uint32_t)r;
+    return q;
+}
+
 // 64-bit mask of the lanes whose `digit` (low `bits` bits significant) equals this lane's, among the lanes in `valid_mask`.
 // FOUR VALU instructions per bit: the bit sign-extended by one v_bfe_i32, one v_cmp for the ballot, and "mask & ~(ballot ^ bit)" as one
 // v_bitop3_b32 per half (truth table 0x90 = a & ~(b ^ c)).  The plain form ("mask &= bit ? bal : ~bal") compiles to EIGHT (v_and, two v_cmp,
@@ -84,6 +103,56 @@ __device__ __forceinline__ uint64_t match_digit(uint32_t digit, int bits, uint64
         hi = __builtin_amdgcn_bitop3_b32(hi, (uint32_t)(bal >> 32), (uint32_t)sx, 0x90);
     }
     return ((uint64_t)hi << 32) | lo;
+}
+// The same mask for a digit width known at compile time: the chain fully unrolled -- the same four VALU per bit, and none of what the rolled loop adds
+// to every bit (loop counter, compare, taken branch and the wait state between the v_cmp's SGPR result and its VALU reader).  The first bit reads
+// `valid_mask` as the wave-uniform value it is instead of a per-lane copy of it.  Straight-line code, so the chains of neighbouring items can be
+// interleaved by the scheduler.  The run-time form above stays for widths without an instantiation.
+// (The bit is extracted by a v_bfe_i32 the optimiser cannot see through: with the position a constant it rewrites the builtin into shift-left,
+// compare-with-0 and arithmetic shift right -- three VALU for the sign mask and the ballot where v_bfe_i32 + v_cmp_ne are two.)
+template <int B>
+__device__ __forceinline__ int digit_bit_sx(uint32_t digit) {
+#ifdef GSR_SIMT_SHIM
+    return __builtin_amdgcn_sbfe((int)digit, (unsigned)B, 1u);
+#else
+    int sx;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(sx) : "v"(digit), "n"(B));
+    return sx;
+#endif
+}
+template <int B, int BITS>
+__device__ __forceinline__ void match_digit_step(uint32_t digit, uint32_t& lo, uint32_t& hi) {
+    if constexpr (B < BITS) {
+        const int sx = digit_bit_sx<B>(digit);      // 0 / -1
+        const uint64_t bal = __ballot(sx != 0);
+        lo = __builtin_amdgcn_bitop3_b32(lo, (uint32_t)bal, (uint32_t)sx, 0x90);
+        hi = __builtin_amdgcn_bitop3_b32(hi, (uint32_t)(bal >> 32), (uint32_t)sx, 0x90);
+        match_digit_step<B + 1, BITS>(digit, lo, hi);
+    }
+}
+template <int BITS>
+__device__ __forceinline__ uint64_t match_digit(uint32_t digit, uint64_t valid_mask) {
+    static_assert(BITS >= 1 && BITS <= 16, "digit width");
+    uint32_t lo = (uint32_t)valid_mask, hi = (uint32_t)(valid_mask >> 32);
+    match_digit_step<0, BITS>(digit, lo, hi);
+    return ((uint64_t)hi << 32) | lo;
+}
+// BITS = 0: the run-time width (one source for both forms of a ranking kernel)
+template <int BITS>
+__device__ __forceinline__ uint64_t match_digit_w(uint32_t digit, int bits, uint64_t valid_mask) {
+    if constexpr (BITS > 0) return match_digit<BITS>(digit, valid_mask);
+    else return match_digit(digit, bits, valid_mask);
+}
+
+// Number of lanes below this one that are set in `mask` = popcount(mask & lt_mask), lt_mask = (1 << lane) - 1: v_mbcnt_lo / v_mbcnt_hi apply the
+// lane mask themselves -- two VALU instead of two v_and and two v_bcnt.  0 <=> this lane is the lowest one of the mask (the "leader" of the ranking loops).
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask, uint64_t lt_mask) {
+#ifdef GSR_SIMT_SHIM
+    return (uint32_t)__popcll(mask & lt_mask);
+#else
+    (void)lt_mask;
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -31,12 +31,15 @@ using namespace gsrw;
 
 namespace {
 
-// (Both ranking kernels run at four waves per SIMD -- 126 / 107 VGPRs -- and spend half of their wave-cycles waiting (SQ_WAIT_ANY).  Forcing five / six
+// (Both ranking kernels run at four waves per SIMD -- 126 / 107 VGPRs with the run-time digit width when this was measured, 104-110 in the width
+// instantiations of today, profiles/isa_ranking.json -- and spend half of their wave-cycles waiting (SQ_WAIT_ANY).  Forcing five / six
 // with amdgpu_waves_per_eu spills 6-25 registers inside the ranking loops: emission 0.053 -> 0.076 ms, tile sort 0.042 -> 0.051 / 0.059 ms,
 // profiles/r05_ab_ranking_occupancy.json.)
 constexpr int TS_ITEMS = GSR_TS_ITEMS;              // instances per workgroup
 constexpr int TS_IPT = TS_ITEMS / WG_THREADS;       // 16 per thread
 constexpr int TS_MAXBINS = 256;
+constexpr int TS_MAX_FUSED_TILES = 65536;           // gsr_tile_sort_plan: more tiles take the LSD path (sort.hip)
+static_assert(TS_MAX_FUSED_TILES <= (1 << 24) && TS_MAX_FUSED_TILES <= (1 << 16), "generate_instances<., true>: every factor of its 24-bit multiplies is bounded by the tile count");
 
 template <typename WordT> struct Pack;
 template <> struct Pack<uint32_t> {
@@ -64,7 +67,10 @@ template <> struct Pack<uint64_t> {
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int TS_NGCAP = 1024;      // Gaussians per block whose record is staged in LDS (beyond: global fetch)
 
-template <bool WANT_ID>
+// MUL24: the divisions and the row product of the expansion with 24-bit multiplies (mul_u24: one issue slot against four of v_mul_lo_u32, 34 of
+// them per thread).  Holds for the 32-bit-word emission of the fused path: at most TS_MAX_FUSED_TILES tiles, so the instance index inside a
+// rectangle, the rectangle's width, the tile row and gx are all <= 2^16 (static_assert at TS_MAX_FUSED_TILES, checked again by the launcher).
+template <bool WANT_ID, bool MUL24>
 __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uint2* __restrict__ block_first,
                                                    const uint32_t* __restrict__ offsets, const uint2* __restrict__ rect_sorted,
                                                    const uint32_t* __restrict__ order, uint16_t* s_own /*[TS_ITEMS]*/,
@@ -124,8 +130,13 @@ __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uin
         if (WANT_ID) id[r] = g.w;
         const uint32_t minx = g.y & 0xFFFFu, wd = (g.y >> 16) - minx, miny = g.z & 0xFFFFu;
         uint32_t rx;
-        const uint32_t ry = div_small((k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
-        tile[r] = (miny + ry) * (uint32_t)gx + minx + rx;
+        if (MUL24) {
+            const uint32_t ry = div_small24((k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
+            tile[r] = mul_u24(miny + ry, (uint32_t)gx) + minx + rx;
+        } else {
+            const uint32_t ry = div_small((k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
+            tile[r] = (miny + ry) * (uint32_t)gx + minx + rx;
+        }
     };
     // Two separate loops on a workgroup-uniform condition.  Written as one loop with "i < TS_NGCAP ? LDS record : global
     // fetch" per item, the compiler merged the two sources into a pointer select and FOUR flat_load_dword per item (the LDS
@@ -204,7 +215,8 @@ emit_hist(uint32_t R, int gx, int lb, int nb1, const uint2* __restrict__ block_f
 // Stable scatter of the workgroup's items by `digit` (< nbins <= 256, `bits` significant bits): returns through LDS
 // the items in workgroup-local sorted order (s_word / s_dig) and the global base of every digit (digit_base, already
 // offset so that global position = digit_base[d] + local index).  ranks: wave64 ballot matching, no atomics.
-template <typename WordT>
+// BITS > 0: the digit width as a compile-time constant (== bits; match_digit<BITS>), 0: the run-time width.
+template <typename WordT, int BITS>
 __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], uint32_t (&digit)[TS_IPT] /*clobbered*/, uint32_t vmask,
                                                   int bits, int nbins, uint32_t my_digit_base /*thread d: global base of digit d*/,
                                                   uint32_t (*wave_cnt)[TS_MAXBINS], uint32_t* digit_base, uint32_t* wsum,
@@ -221,11 +233,12 @@ __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], u
     for (int r = 0; r < TS_IPT; ++r) {
         const bool valid = (vmask >> r) & 1u;
         const uint32_t d = digit[r];
-        const uint64_t mask = match_digit(d, bits, __ballot(valid));
+        const uint64_t mask = match_digit_w<BITS>(d, bits, __ballot(valid));
         const uint32_t prior = valid ? wave_cnt[w][d] : 0u;
+        const uint32_t below = lanes_below(mask, lt_mask);
         // the item's rank among the wave's items of its digit rides in the upper half of the digit word (rank < 4096)
-        digit[r] = d | ((prior + (uint32_t)__popcll(mask & lt_mask)) << 16);
-        if (valid && (mask & lt_mask) == 0ull) wave_cnt[w][d] = prior + (uint32_t)__popcll(mask);
+        digit[r] = d | ((prior + below) << 16);
+        if (valid && below == 0u) wave_cnt[w][d] = prior + (uint32_t)__popcll(mask);
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
@@ -261,7 +274,8 @@ __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], u
 }
 
 // level 1 scatter (+ first-emission indices for the backward, + the bucket tables of level 2 from block 0)
-template <typename WordT>
+// HB > 0: the bucket digit's width as a compile-time constant (== hb), 0: the generic kernel.  MUL24: generate_instances
+template <typename WordT, int HB, bool MUL24>
 __global__ void __launch_bounds__(WG_THREADS)
 emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block_first, const uint32_t* __restrict__ offsets,
              const uint2* __restrict__ rect_sorted, const uint32_t* __restrict__ order, const uint32_t* __restrict__ hist,
@@ -282,12 +296,13 @@ emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block
     WordT* s_word = reinterpret_cast<WordT*>(smem);
     uint8_t* s_dig = smem + TS_ITEMS * sizeof(WordT);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (HB) hb = HB;
     const int nb1 = 1 << hb;
     // independent of everything else: requested first
     const uint32_t my_total = tid < nb1 ? digit_total[tid] : 0u;
     const uint32_t my_hist = tid < nb1 ? hist[(int64_t)tid * nblk + blockIdx.x] : 0u;
     uint32_t tile[TS_IPT], id[TS_IPT], vmask;
-    generate_instances<true>(R, gx, block_first, offsets, rect_sorted, order, s_own, s_g4, wsum, splats, tile, id, vmask);
+    generate_instances<true, MUL24>(R, gx, block_first, offsets, rect_sorted, order, s_own, s_g4, wsum, splats, tile, id, vmask);
     // global base of bucket d for this block = exclusive scan of the bucket totals + instances of earlier blocks
     uint32_t tot[1] = {my_total};
     const uint32_t bbase = block_excl_scan<1>(tot, wsum, lane, w);
@@ -316,7 +331,7 @@ emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block
     }
     // (the barriers at the top of local_stable_sort separate the last read of the generation arrays from the first write
     // of the word staging that shares their LDS)
-    local_stable_sort<WordT>(word, digit, vmask, hb, nb1, bbase + my_hist, wave_cnt, digit_base, wsum, s_word, s_dig);
+    local_stable_sort<WordT, HB>(word, digit, vmask, hb, nb1, bbase + my_hist, wave_cnt, digit_base, wsum, s_word, s_dig);
     const uint32_t b0 = blockIdx.x * (uint32_t)TS_ITEMS;
     const uint32_t nvalid = R - b0 < (uint32_t)TS_ITEMS ? R - b0 : (uint32_t)TS_ITEMS;
 #pragma unroll
@@ -441,7 +456,8 @@ bucket_scan(int lb, int h0, int n_tiles, const uint32_t* __restrict__ bucket_bas
 // digit, the counts of its bucket's workgroups (all of them: the per-tile bases; those before it: its own offsets) in one round
 // of independent loads.  The bucket's first workgroup writes the tile ranges.  Chosen by the host while a bucket has few
 // workgroups (the slab a workgroup reads is workgroups-per-bucket x nb2 x 4 bytes).
-template <typename WordT, bool FUSED_SCAN>
+// LB > 0: the low digit's width as a compile-time constant (== lb), 0: the generic kernel
+template <typename WordT, bool FUSED_SCAN, int LB>
 __global__ void __launch_bounds__(WG_THREADS)
 bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, const uint32_t* __restrict__ bucket_base,
                const uint32_t* __restrict__ blk2_start, const uint32_t* __restrict__ hist2,
@@ -453,6 +469,7 @@ bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, 
     __shared__ uint8_t s_dig[TS_ITEMS];
     __shared__ int s_h[5];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (LB) lb = LB;
     const int nb1 = 1 << hb, nb2 = 1 << lb;
     uint32_t h, begin, end, B2;
     if (!bucket_block(nb1, h0, h1, bucket_base, blk2_start, s_h, h, begin, end, B2)) return;
@@ -513,7 +530,7 @@ bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, 
     } else {
         my_base = tid < nb2 ? tile_base[h * (uint32_t)nb2 + tid] + hist2[(int64_t)B2 * nb2 + tid] : 0u;
     }
-    local_stable_sort<uint32_t>(id, digit, vmask, lb, nb2, my_base, wave_cnt, digit_base, wsum, s_id, s_dig);
+    local_stable_sort<uint32_t, LB>(id, digit, vmask, lb, nb2, my_base, wave_cnt, digit_base, wsum, s_id, s_dig);
     const uint32_t nvalid = end - begin;
 #pragma unroll
     for (int r = 0; r < TS_IPT; ++r) {
@@ -565,12 +582,24 @@ void gsr_launch_tile_sort_level1(const GsrTileSortPlan& plan, int64_t R, int gx,
     hipLaunchKernelGGL(emit_hist, dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, nb1, block_first, offsets, rect_sorted,
                        hist1, nblk);
     gsr_launch_rs_scan(hist1, nblk, nb1, digit_total, st);
-    if (plan.word64)
-        hipLaunchKernelGGL(emit_scatter<uint64_t>, dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, plan.hb, block_first,
-                           offsets, rect_sorted, order, hist1, digit_total, nblk, (uint64_t*)words, bucket_base, blk2_start, splats);
-    else
-        hipLaunchKernelGGL(emit_scatter<uint32_t>, dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, plan.hb, block_first,
-                           offsets, rect_sorted, order, hist1, digit_total, nblk, (uint32_t*)words, bucket_base, blk2_start, splats);
+#define GSR_L1_SCATTER(WORD_, HB_, MUL24_)                                                                                                          \
+    hipLaunchKernelGGL((emit_scatter<WORD_, HB_, MUL24_>), dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, plan.hb, block_first, offsets,   \
+                       rect_sorted, order, hist1, digit_total, nblk, (WORD_*)words, bucket_base, blk2_start, splats)
+    // The 24-bit multiplies of the expansion need the fused path's tile bound (every factor <= the tile count <= 2^16): a plan of at most 16 tile-id
+    // bits says so.  The 64-bit-word kernel, and any caller outside that bound, keep the full multiplies.
+    const bool mul24 = plan.fused && plan.lb + plan.hb <= 16 && gx <= TS_MAX_FUSED_TILES;
+    // (no instantiation for 8 bits -- frames beyond 32768 tiles: its sixteen live ballots push two SGPRs out into VGPR lanes)
+    const int hb_inst = (plan.word64 || !mul24 || g_ranking_generic || plan.hb < 5 || plan.hb > 7) ? 0 : plan.hb;
+    g_ranking_last_hb = hb_inst;
+    if (plan.word64) GSR_L1_SCATTER(uint64_t, 0, false);
+    else if (!mul24) GSR_L1_SCATTER(uint32_t, 0, false);
+    else switch (hb_inst) {      // the bucket digit's width of real frames (640x360 ... 4K) has an instantiation of its own
+        case 5: GSR_L1_SCATTER(uint32_t, 5, true); break;
+        case 6: GSR_L1_SCATTER(uint32_t, 6, true); break;
+        case 7: GSR_L1_SCATTER(uint32_t, 7, true); break;
+        default: GSR_L1_SCATTER(uint32_t, 0, true); break;
+    }
+#undef GSR_L1_SCATTER
 }
 
 int g_level2_scan_mode = 0;      // option level2_scan_mode: 0 = automatic, 1 = separate bucket_scan launch, 2 = folded into bucket_scatter
@@ -601,10 +630,22 @@ void gsr_launch_tile_sort_level2(const GsrTileSortPlan& plan, int64_t R, int n_t
     if (!fused)
         hipLaunchKernelGGL(bucket_scan, dim3(h1 - h0), dim3(WG_THREADS), 0, st, plan.lb, h0, n_tiles, bucket_base, blk2_start, hist2, tile_base,
                            ranges);
-#define GSR_L2_SCATTER(WORD_, FUSED_)                                                                                               \
-    hipLaunchKernelGGL((bucket_scatter<WORD_, FUSED_>), dim3(nblk2), dim3(WG_THREADS), 0, st, plan.lb, plan.hb, h0, h1, (const WORD_*)words,  \
+#define GSR_L2_SCATTER(WORD_, FUSED_, LB_)                                                                                              \
+    hipLaunchKernelGGL((bucket_scatter<WORD_, FUSED_, LB_>), dim3(nblk2), dim3(WG_THREADS), 0, st, plan.lb, plan.hb, h0, h1, (const WORD_*)words,  \
                        bucket_base, blk2_start, hist2, tile_base, point_list, ranges, n_tiles)
-    if (plan.word64) { if (fused) GSR_L2_SCATTER(uint64_t, true); else GSR_L2_SCATTER(uint64_t, false); }
-    else { if (fused) GSR_L2_SCATTER(uint32_t, true); else GSR_L2_SCATTER(uint32_t, false); }
+#define GSR_L2_SCATTER_W(FUSED_)                                                                                                            \
+    switch (lb_inst) {      /* the low digit's width of real frames has an instantiation of its own */                                    \
+        case 5: GSR_L2_SCATTER(uint32_t, FUSED_, 5); break;                                                                                 \
+        case 6: GSR_L2_SCATTER(uint32_t, FUSED_, 6); break;                                                                                 \
+        case 7: GSR_L2_SCATTER(uint32_t, FUSED_, 7); break;                                                                                 \
+        case 8: GSR_L2_SCATTER(uint32_t, FUSED_, 8); break;                                                                                 \
+        default: GSR_L2_SCATTER(uint32_t, FUSED_, 0); break;                                                                                \
+    }
+    const int lb_inst = (plan.word64 || g_ranking_generic || plan.lb < 5 || plan.lb > 8) ? 0 : plan.lb;
+    g_ranking_last_lb = lb_inst;
+    if (plan.word64) { if (fused) GSR_L2_SCATTER(uint64_t, true, 0); else GSR_L2_SCATTER(uint64_t, false, 0); }
+    else if (fused) { GSR_L2_SCATTER_W(true) }
+    else { GSR_L2_SCATTER_W(false) }
+#undef GSR_L2_SCATTER_W
 #undef GSR_L2_SCATTER
 }

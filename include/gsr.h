@@ -830,7 +830,12 @@ int gsr_profile_trace(uint64_t* out, int max_waves);
  *                    16-coefficient SH fused or dc / rest, band of a quarter of the frame or more: no dead paths), 1 = always the generic one
  *                    (A/B and tests; the same bits either way)
  *   preprocess_hot_grid workgroups of those instantiations: 0 (default) = one resident round, from the occupancy the runtime reports; 1..2047
+ *   ranking_generic  0 (default) = the stable-ranking kernels of the binning chain (emit_scatter, bucket_scatter, ds_segsort) run the
+ *                    instantiation compiled for the frame's digit width (tile-id halves of 5..8 bits, bucket digit 5..7: 640x360 up to 4K), 1 = always the
+ *                    run-time-width one (A/B and tests; the same bits either way)
  * Test hook: debug_last_preprocess_path = 1 (generic) / 2 (hot) changes nothing and succeeds iff the most recent forward took that instantiation.
+ * Test hook: debug_last_ranking_widths = hb << 4 | lb changes nothing and succeeds iff the most recent tile sort ran emit_scatter instantiated for
+ * hb bits and bucket_scatter for lb bits (0: the run-time-width kernel).
  * Test hook: debug_dirty_control_block = t preloads t tickets into the frame counter of the NEXT forward call, once (a counter that is
  * not zero when a frame begins, csrc/gsr_frame.h): that frame is wrong or refused, the ones after it must be right again. */
 int gsr_set_option(const char* name, int value);

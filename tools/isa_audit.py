@@ -164,7 +164,78 @@ def preprocess_forward(source=None, extra=()):
     return sorted(rows, key=lambda r: (r["form"] != "hot", r["split_sh"]))
 
 
+RANKING_KERNELS = {"tilesort.hip": ("emit_scatter", "bucket_scatter"), "depthsort.hip": ("ds_scatter", "ds_segsort")}
+
+
+def _template_args(mangled: str, kernel: str) -> str:
+    """'<uint32_t, 6, true>' from the Itanium mangling of an instantiation of `kernel` (j = uint32_t, m = uint64_t, Lb / Li literals)."""
+    m = re.search(kernel + r"I((?:[jm]|L[bi]\d+E)+)E", mangled)
+    if not m:
+        return ""
+    out = []
+    for a in re.findall(r"[jm]|L[bi]\d+E", m.group(1)):
+        out.append({"j": "uint32_t", "m": "uint64_t"}.get(a) or (("true" if a[2:-1] == "1" else "false") if a[1] == "b" else a[2:-1]))
+    return "<" + ", ".join(out) + ">"
+
+
+def ranking(source_dir=None, extra=()):
+    """Every instantiation of the four stable-ranking kernels of the binning chain (csrc/tilesort.hip emit_scatter / bucket_scatter, csrc/depthsort.hip
+    ds_scatter / ds_segsort), one dict each: static counts over the whole kernel of VALU, SALU, v_mov_b32, v_mul_lo_u32, v_bitop3_b32 (two per
+    matched bit and item: an unrolled match chain of BITS bits over ITEMS items shows as 2 x BITS x ITEMS, a rolled one as 2), v_bcnt / v_mbcnt;
+    from the code-object metadata VGPRs, spills, scratch and LDS bytes, and the waves per SIMD the compiler states.
+    `source_dir`: another copy of csrc/ (the parent's, for the committed before / after pair in profiles/).
+        python tools/isa_audit.py ranking [dir]      # prints JSON"""
+    rows = []
+    for unit, kernels in RANKING_KERNELS.items():
+        src = os.path.join(source_dir or CSRC, unit)
+        with tempfile.TemporaryDirectory() as td:
+            out = os.path.join(td, "k.s")
+            cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + (source_dir or CSRC), "-S",
+                   "--cuda-device-only", "-o", out, src] + UNITS[unit] + list(extra)
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(r.stderr[-2000:])
+            s = open(out).read()
+        meta = {}
+        for entry in re.split(r"^  - (?=\.)", s[s.index("amdhsa.kernels:"):], flags=re.M)[1:]:
+            f = dict(re.findall(r"^\s*\.(\w+):\s*(\S+)\s*$", entry, re.M))
+            meta[f["name"]] = f
+        for m in re.finditer(r"^(_Z\w+): ; @.*?\n(.*?)^\.Lfunc_end\d+:(.*?^; Occupancy:\s*\d+)", s, re.S | re.M):
+            name, body, trailer = m.group(1), m.group(2), m.group(3)
+            kernel = next((k for k in kernels if re.search(r"\d" + k + r"[IE]", name)), None)
+            if kernel is None or name not in meta:
+                continue
+            f = meta[name]
+            ops = [t[0] for t in (line.strip().split() for line in body.split("\n")) if t and not t[0].startswith((";", ".")) and not t[0].endswith(":")]
+            occ = re.search(r"; Occupancy:\s*(\d+)", trailer)
+            # the truth tables of the kernel's v_bitop3_b32: 0x90 = a & ~(b ^ c) is match_digit's; the compiler forms others from plain and / or / xor
+            tables = [x.lower() for x in re.findall(r"^\s+v_bitop3_b32\s.*?bitop3:(0x[0-9a-fA-F]+)", body, re.M)]
+            rows.append({
+                "unit": unit, "kernel": kernel, "instantiation": kernel + _template_args(name, kernel), "symbol": name,
+                "valu": sum(o.startswith("v_") for o in ops), "salu": sum(o.startswith("s_") and o not in ("s_waitcnt", "s_nop") for o in ops),
+                "v_mov_b32": sum(o.startswith("v_mov_b32") for o in ops), "v_mul_lo_u32": sum(o.startswith("v_mul_lo_u32") for o in ops),
+                "v_mul_u32_u24": sum(o.startswith(("v_mul_u32_u24", "v_mad_u32_u24")) for o in ops),
+                "v_bitop3_b32": sum(o.startswith("v_bitop3_b32") for o in ops), "v_bitop3_b32_match": tables.count("0x90"),
+                "v_bfe_i32": sum(o.startswith("v_bfe_i32") for o in ops),
+                "v_bcnt_u32_b32": sum(o.startswith("v_bcnt_u32_b32") for o in ops), "v_mbcnt": sum(o.startswith("v_mbcnt") for o in ops),
+                "s_nop": ops.count("s_nop"), "branches": sum(o.startswith(("s_cbranch", "s_branch")) for o in ops),
+                "vgprs": int(f["vgpr_count"]), "agprs": int(f.get("agpr_count", 0)), "sgprs": int(f["sgpr_count"]),
+                "vgpr_spill_count": int(f["vgpr_spill_count"]), "sgpr_spill_count": int(f["sgpr_spill_count"]),
+                "scratch_bytes": int(f["private_segment_fixed_size"]), "lds_bytes": int(f["group_segment_fixed_size"]),
+                "waves_per_simd": int(occ.group(1)) if occ else None,
+            })
+    if not rows:
+        raise RuntimeError("no ranking kernel found")
+    return sorted(rows, key=lambda r: (r["unit"] != "tilesort.hip", r["kernel"], r["instantiation"]))
+
+
 def main():
+    if sys.argv[1:2] == ["ranking"]:
+        import json
+        dirs = [a for a in sys.argv[2:] if not a.startswith("-")]
+        print(json.dumps({"units": {u: UNITS[u] for u in RANKING_KERNELS}, "items_per_thread": {"emit_scatter": 16, "bucket_scatter": 16, "ds_scatter": 8, "ds_segsort": 1},
+                          "instantiations": ranking(dirs[0] if dirs else None, [a for a in sys.argv[2:] if a.startswith("-")])}, indent=1))
+        return
     if sys.argv[1:2] == ["preprocess_forward"]:
         import json
         srcs = [a for a in sys.argv[2:] if not a.startswith("-")]
