@@ -12,6 +12,9 @@ Translation units and their flags:
                                         test, exponent / alpha -- is csrc/gsr_blend.h, their wave reductions csrc/gsr_wave.h)
   bilagrid.hip     -ffp-contract=fast -fno-slp-vectorize   (the image kernels' flags: the trilinear blend is 96 multiply-adds per pixel, tolerance
                                         1e-5; the pixel -> cell map is products only, nothing in it contracts; total variation is fp64)
+  normals.hip      -ffp-contract=fast -fno-slp-vectorize   (the image kernels' flags: the depth differences are single subtractions, which
+                                        contraction cannot touch; fused products only shorten the rounding chain behind them; bars <= 2e-6, the
+                                        loss sum is fp64)
   gsr_api.cpp                          (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
@@ -63,6 +66,7 @@ UNITS = [
     ("density.hip", ["-ffp-contract=off"]),
     ("mcmc.hip", ["-ffp-contract=off"]),
     ("bilagrid.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
+    ("normals.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

@@ -1720,6 +1720,84 @@ int gsr_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, c
     return GSR_OK;
 }
 
+// ---- normals (normals.hip) ----
+int gsr_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, float* normals_out,
+                         void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!scales || !rotations || !means3D || !viewmatrix || !normals_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_gaussian_normals(P, scales, rotations, means3D, viewmatrix, normals_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_gaussian_normals_backward(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix,
+                                  const float* dL_dnormals, float* dL_drotations, void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!scales || !rotations || !means3D || !viewmatrix || !dL_dnormals || !dL_drotations) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_gaussian_normals_backward(P, scales, rotations, means3D, viewmatrix, dL_dnormals, dL_drotations, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+static int normals_frame_checked(int H, int W, float tanfovx, float tanfovy, GsrNormalsFrame* f) {
+    if (H < 1 || W < 1) return fail(GSR_ERR_INVALID_ARG, "normals: image size must be positive, got " + std::to_string(H) + " x " + std::to_string(W));
+    if ((int64_t)H * W > 0x7FFFFFFFll) return fail(GSR_ERR_UNSUPPORTED, "normals: more than 2^31-1 pixels");
+    if (!(tanfovx > 0.f) || !(tanfovy > 0.f) || !std::isfinite(tanfovx) || !std::isfinite(tanfovy))
+        return fail(GSR_ERR_INVALID_ARG, "normals: tanfovx and tanfovy must be positive and finite, got " + std::to_string(tanfovx) + ", " +
+                                             std::to_string(tanfovy));
+    gsr_normals_frame(H, W, tanfovx, tanfovy, f);
+    return GSR_OK;
+}
+
+int gsr_depth_normals(int H, int W, float tanfovx, float tanfovy, const float* depth, float* normals_out, void* stream) {
+    GsrNormalsFrame f;
+    if (int rc = normals_frame_checked(H, W, tanfovx, tanfovy, &f)) return rc;
+    if (!depth || !normals_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_depth_normals(f, depth, normals_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_depth_normals_backward(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* dL_dnormals, float* dL_ddepth,
+                               void* stream) {
+    GsrNormalsFrame f;
+    if (int rc = normals_frame_checked(H, W, tanfovx, tanfovy, &f)) return rc;
+    if (!depth || !dL_dnormals || !dL_ddepth) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_depth_normals_backward(f, depth, dL_dnormals, dL_ddepth, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int64_t gsr_normal_loss_partial_count(int H, int W) {
+    GsrNormalsFrame f;
+    if (normals_frame_checked(H, W, 1.f, 1.f, &f) != GSR_OK) return 0;
+    return gsr_normals_tiles(f);
+}
+
+int gsr_normal_loss(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* normals, const float* weight, double* partials,
+                    float* loss_out, void* stream) {
+    GsrNormalsFrame f;
+    if (int rc = normals_frame_checked(H, W, tanfovx, tanfovy, &f)) return rc;
+    if (!depth || !normals || !partials || !loss_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only weight may be NULL)");
+    if ((uintptr_t)partials & 7) return fail(GSR_ERR_INVALID_ARG, "normals: partials must be 8-byte aligned");
+    gsr_launch_normal_loss(f, depth, normals, weight, partials, loss_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_normal_loss_backward(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* normals, const float* weight,
+                             const float* dL_dloss, float* dL_dnormals, float* dL_ddepth, void* stream) {
+    GsrNormalsFrame f;
+    if (int rc = normals_frame_checked(H, W, tanfovx, tanfovy, &f)) return rc;
+    if (!depth || !normals || !dL_dloss) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only weight, dL_dnormals and dL_ddepth may be NULL)");
+    if (!dL_dnormals && !dL_ddepth) return GSR_OK;
+    gsr_launch_normal_loss_backward(f, depth, normals, weight, dL_dloss, dL_dnormals, dL_ddepth, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

@@ -464,6 +464,29 @@ void gsr_launch_bilagrid_slice_backward(const GsrBilagridPlan& p, const float* g
 int64_t gsr_bilagrid_tv_partial_count_impl(int N, int L, int Gh, int Gw);
 void gsr_launch_bilagrid_tv(int N, int L, int Gh, int Gw, const float* grids, double* partials, float* tv_out, hipStream_t st);
 void gsr_launch_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, const float* dL_dtv, float* dL_dgrids, hipStream_t st);
+// normals.hip: per-Gaussian normals, normals of a depth map and the fused normal-consistency loss.  The frame record holds the
+// fp32 constants of the pixel -> ray map, rounded once on the host from fp64, and the tile grid (64 x 16 pixels per workgroup): the host sizes
+// the loss partials with it and the kernels take it by value.
+struct GsrNormalsFrame {
+    int H, W, tiles_x, tiles_y;
+    float tx, ty;                 // tanfovx, tanfovy
+    float inv_w, inv_h;           // 1 / W, 1 / H
+    float alpha, beta, ab;        // tanfovy 2 / H, tanfovx 2 / W, their product
+    float inv_hw;                 // 1 / (H W)
+};
+void gsr_normals_frame(int H, int W, float tanfovx, float tanfovy, GsrNormalsFrame* out);
+static inline int gsr_normals_tiles(const GsrNormalsFrame& f) { return f.tiles_x * f.tiles_y; }
+void gsr_launch_gaussian_normals(int P, const float* scales, const float* rot, const float* means, const float* vm, float* out, hipStream_t st);
+void gsr_launch_gaussian_normals_backward(int P, const float* scales, const float* rot, const float* means, const float* vm, const float* dn,
+                                          float* drot, hipStream_t st);
+void gsr_launch_depth_normals(const GsrNormalsFrame& f, const float* depth, float* out, hipStream_t st);
+void gsr_launch_depth_normals_backward(const GsrNormalsFrame& f, const float* depth, const float* dL_dnormals, float* dL_ddepth, hipStream_t st);
+// weight may be NULL; partials: gsr_normals_tiles(f) doubles
+void gsr_launch_normal_loss(const GsrNormalsFrame& f, const float* depth, const float* normals, const float* weight, double* partials,
+                            float* loss_out, hipStream_t st);
+// dL_dnormals or dL_ddepth may be NULL (both: no launch); each is the same bits whether or not the other is asked for
+void gsr_launch_normal_loss_backward(const GsrNormalsFrame& f, const float* depth, const float* normals, const float* weight,
+                                     const float* dL_dloss, float* dL_dnormals, float* dL_ddepth, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

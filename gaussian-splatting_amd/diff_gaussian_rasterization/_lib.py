@@ -162,6 +162,13 @@ SIGNATURES = {
     "gsr_bilagrid_tv_partial_count": (C.c_int64, [C.c_int] * 4),
     "gsr_bilagrid_tv": (C.c_int, [C.c_int] * 4 + [_vp] * 4),
     "gsr_bilagrid_tv_backward": (C.c_int, [C.c_int] * 4 + [_vp] * 4),
+    "gsr_gaussian_normals": (C.c_int, [C.c_int] + [_vp] * 6),
+    "gsr_gaussian_normals_backward": (C.c_int, [C.c_int] + [_vp] * 7),
+    "gsr_depth_normals": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 3),
+    "gsr_depth_normals_backward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 4),
+    "gsr_normal_loss_partial_count": (C.c_int64, [C.c_int] * 2),
+    "gsr_normal_loss": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 6),
+    "gsr_normal_loss_backward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 7),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

@@ -698,6 +698,54 @@ int gsr_bilagrid_tv(int N, int L, int Gh, int Gw, const float* grids, double* pa
 int gsr_bilagrid_tv_backward(int N, int L, int Gh, int Gw, const float* grids, const float* dL_dtv, float* dL_dgrids, void* stream);
 
 /*
+ * Normal-consistency regulariser (2DGS, GOF, RaDe-GS, PGSR): per-Gaussian normals, the normals of a depth map, and the fused loss
+ *   loss = (1 / (H W)) sum_p [1 - w(p) <normals(p), Nd(p)>].                                  (Additive, the ABI version stays 4.)
+ *
+ * Per-Gaussian normals, camera space, normals_out[P,3].  For row g: s = scales[g] (activated), q = rotations[g] (w first) AS GIVEN -- R(q) is
+ * the matrix the rasterizer builds from q and is not normalised; k = the index of the smallest s (lowest index on exact ties); a = column k of
+ * R(q); v_i = vm[i] a0 + vm[4 + i] a1 + vm[8 + i] a2 (the rotation part of `viewmatrix`, the flat 16 floats of the rasterizer's settings, a
+ * device pointer); n = v / |v|; with p the view-space mean of means3D[g], n = -n when <n, p> > 0 (normals face the camera).  The backward
+ * writes dL_drotations[P,4] through a(q) and the normalisation; k and the sign are constants, recomputed from the inputs (no saved state); no
+ * gradient goes to scales, means3D or the camera.  A row with a non-finite input, or with |v| zero or non-finite, gets n = 0 and a zero
+ * gradient row.  P == 0 is a no-op.
+ *
+ * NUMERICS CONTRACT of the depth normals.  depth is [H,W] fp32 (the z of the camera-space point seen by the pixel), normals are planar [3,H,W].
+ * Pixel (x, y) has nx = (2 x + 1) / W - 1, ny = (2 y + 1) / H - 1 and the point p = (nx tanfovx z, ny tanfovy z, z): the rasterizer's pixel
+ * centres (pix = ((ndc + 1) W - 1) / 2, centred principal point).  For an interior pixel (1 <= x <= W - 2, 1 <= y <= H - 2), with
+ *   dz = z(x+1, y) - z(x-1, y),  sz = their sum;   dz' = z(x, y+1) - z(x, y-1),  sz' = their sum:
+ *   du = (tanfovx (nx dz + (2 / W) sz),  ny tanfovy dz,  dz)          (= p(x+1, y) - p(x-1, y))
+ *   dv = (nx tanfovx dz',  tanfovy (ny dz' + (2 / H) sz'),  dz')      (= p(x, y+1) - p(x, y-1))
+ *   c = dv x du,   Nd = c / |c|.
+ * A fronto-parallel plane gives (0, 0, -1): normals face the camera (2DGS's orientation, in camera space).  The depth differences are formed
+ * BEFORE any multiplication by the ray -- differencing back-projected points cancels in fp32 with an error that grows with the resolution;
+ * this form stays at a few 1e-7 at every size.  (The kernels evaluate c in the algebraically identical closed form in which the products
+ * dz dz' of the two tangents, which cancel identically, are never formed.)
+ * Nd = 0 at border pixels, where any of the five stencil depths (centre included) is not a finite positive number, and where |c| is zero or
+ * not finite.  A poisoned depth pixel therefore changes Nd at itself and its four neighbours only, and dL/ddepth within Manhattan distance 2
+ * only; every other output keeps its bits.  The gradient of the normalisation is (g - N <N, g>) / |c|; validity and the border carry none.
+ * H or W below 3 is valid: every pixel is border, the map is zero and the loss is exactly 1.  tanfovx, tanfovy must be positive and finite.
+ *
+ * The loss: `weight` [H,W] is optional (NULL: 1) and a constant (2DGS passes the detached alpha).  Nd is never written to memory.  A pixel with
+ * Nd = 0 or weight 0 contributes exactly 1 and exact zero gradients whatever `normals` holds there, NaN included.  The forward writes one fp64
+ * partial sum per workgroup into `partials` (gsr_normal_loss_partial_count doubles, 8-byte aligned) and their sum, added in index order and
+ * divided by H W, into loss_out[1].  The backward takes dL/dloss as ONE device scalar and writes dL_dnormals [3,H,W] and / or dL_ddepth [H,W]
+ * (either may be NULL; each has the same bits whether or not the other is asked for).  No floating-point atomics anywhere: two runs give the
+ * same bits.
+ */
+int gsr_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, float* normals_out,
+                         void* stream);
+int gsr_gaussian_normals_backward(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix,
+                                  const float* dL_dnormals, float* dL_drotations, void* stream);
+int gsr_depth_normals(int H, int W, float tanfovx, float tanfovy, const float* depth, float* normals_out, void* stream);
+int gsr_depth_normals_backward(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* dL_dnormals, float* dL_ddepth,
+                               void* stream);
+int64_t gsr_normal_loss_partial_count(int H, int W);                          /* 0: unsupported sizes */
+int gsr_normal_loss(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* normals, const float* weight_or_null,
+                    double* partials, float* loss_out, void* stream);
+int gsr_normal_loss_backward(int H, int W, float tanfovx, float tanfovy, const float* depth, const float* normals, const float* weight_or_null,
+                             const float* dL_dloss, float* dL_dnormals_or_null, float* dL_ddepth_or_null, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points

@@ -15,7 +15,8 @@ What is mirrored from the reference (train.py:73-190, arguments/__init__.py:72-1
   * density statistics every iteration and clone / split / prune every 100 iterations from 500 to 15 000 with gradient
     threshold 0.0002, opacity floor 0.005, screen-size pruning after iteration 3000, opacity reset every 3000 iterations
     (train.py:160-174, arguments/__init__.py:91-95).
-Beyond the reference, off by default: `--bilateral_grid`, gsplat's per-image appearance compensation (fused_bilagrid).
+Beyond the reference, off by default: `--bilateral_grid`, gsplat's per-image appearance compensation (fused_bilagrid, INTEGRATION.md 3j);
+`--normal_consistency`, the depth-normal consistency regulariser of 2DGS (gsr_normals).
 Reported: iterations/s (whole run and per 5000-iteration window), the Gaussian count over time, peak device memory, the
 largest R-sized scratch buffers.  One JSON line on stdout (also written to gpurun_out/train_run.json)."""
 from __future__ import annotations
@@ -66,6 +67,9 @@ def main():
     ap.add_argument("--bilateral_grid", action="store_true",
                     help="per-camera appearance compensation (fused_bilagrid.BilateralGrid, 16 x 16 x 8): the rendered image is sliced through its "
                          "camera's grid before the loss, 10 tv_loss is added, the grids have their own gsr_optim.FusedAdam (lr 2e-3)")
+    ap.add_argument("--normal_consistency", type=float, default=0.0, metavar="LAMBDA",
+                    help="add LAMBDA * gsr_normals.normal_consistency_loss (2DGS uses 0.05): per-Gaussian normals and the view-space z rendered as "
+                         "four feature channels with geometry gradients, depth = D / alpha, weight = the detached alpha; 0 (default) = off")
     ap.add_argument("--fuse-sh-step", action="store_true",
                     help="opt-in: the optimizer step of f_dc / f_rest is applied by the per-Gaussian backward kernel "
                          "(diff_gaussian_rasterization.fuse_sh_adam_into_backward); switched off on the iterations that densify, "
@@ -83,6 +87,7 @@ def main():
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, SparseGaussianAdam
     import diff_gaussian_rasterization as dgr
     from fused_ssim import fused_train_loss
+    from gsr_normals import gaussian_normals, normal_consistency_loss
     from gsr_optim import FusedAdam
     from gsr_scene.densify import DensifyStats, densify_and_prune, reset_opacity
 
@@ -184,14 +189,23 @@ def main():
         if a.fuse_sh_step:      # (the tensors change at every densification; no fused step where the loop below replaces them)
             set_fusion(not (500 < it < 15000 and it % 100 == 0) and it < a.iters)
         m2 = torch.zeros(P, 3, device=dev, requires_grad=True)
-        img, radii, _ = GaussianRasterizer(settings(cams[ci], deg))(
+        S = settings(cams[ci], deg)
+        scales_act, rot_act = torch.exp(params["scaling"]), torch.nn.functional.normalize(params["rotation"])
+        out = (GaussianRasterizer(S, return_alpha=True) if a.normal_consistency > 0 else GaussianRasterizer(S))(
             means3D=params["xyz"], means2D=m2, dc=params["f_dc"], shs=params["f_rest"], opacities=torch.sigmoid(params["opacity"]),
-            scales=torch.exp(params["scaling"]), rotations=torch.nn.functional.normalize(params["rotation"]))
+            scales=scales_act, rotations=rot_act)
+        img, radii = out[0], out[1]
         gt = gts[ci]
         if bil is not None:
             loss = fused_train_loss(bil(img, ci), gt, 0.2) + 10.0 * bil.tv_loss()
         else:
             loss = fused_train_loss(img, gt, 0.2)          # train.py:119-126 as one fused kernel pair (L1 + SSIM + mix)
+        if a.normal_consistency > 0:                       # the recipe on this frame's saved state
+            alpha, vm = out[3], S.viewmatrix
+            cols = torch.cat([gaussian_normals(scales_act, rot_act, params["xyz"], vm), (params["xyz"] @ vm[:3, 2] + vm[3, 2])[:, None]], dim=1)
+            feat = dgr.render_features(img, cols, geometry=True)
+            loss_n = normal_consistency_loss(feat[3] / alpha[0].clamp_min(1e-6), feat[:3], S.tanfovx, S.tanfovy, weight=alpha[0].detach())
+            loss = loss + a.normal_consistency * loss_n
         loss.backward()
         with torch.no_grad():
             if it < 15000:
@@ -328,7 +342,8 @@ def main():
            "config": {"workload": f"configs[2] stand-in: P0 {P0} -> densified, {W}x{H}, {len(cams)} synthetic views cycled without "
                                   f"replacement, target scene {a.P_target} Gaussians (SURVEY 8(d) generator, seed {a.seed})",
                       "optimizer": ("FusedAdam (dense)" if a.dense_adam else "SparseGaussianAdam + separate_sh call form") + (" + SH step inside backward (opt-in fusion)" if a.fuse_sh_step else "")
-                                   + (" + per-camera bilateral grids 16x16x8 (slice before the loss, 10 tv_loss, FusedAdam lr 2e-3)" if a.bilateral_grid else ""),
+                                   + (" + per-camera bilateral grids 16x16x8 (slice before the loss, 10 tv_loss, FusedAdam lr 2e-3)" if a.bilateral_grid else "")
+                                   + (f" + {a.normal_consistency:g} x depth-normal consistency (gsr_normals on a 4-channel feature render)" if a.normal_consistency > 0 else ""),
                       "schedule": f"densify 500..15000 every 100 (grad {a.grad_threshold:g}, opacity 0.005, size 20 after 3000), opacity reset / 3000, "
                                   "SH degree +1 / 1000, position lr 1.6e-4 -> 1.6e-6 x extent", "extent": ext},
            "final_P": int(params["xyz"].shape[0]), "max_P": max(sizes + [P0]), "P_every_1000_iters": sizes,
