@@ -15,7 +15,9 @@ Translation units and their flags:
   normals.hip      -ffp-contract=fast -fno-slp-vectorize   (the image kernels' flags: the depth differences are single subtractions, which
                                         contraction cannot touch; fused products only shorten the rounding chain behind them; bars <= 2e-6, the
                                         loss sum is fp64)
-  gsr_api.cpp                          (host glue, C ABI)
+  mip.hip          -ffp-contract=off   (the per-Gaussian streaming kernels' flag: the sweep's dot products are explicit fmaf chains, the
+                                        activations take correctly rounded divide / sqrt through intrinsics)
+  gsr_api.cpp                         (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
 """
@@ -67,6 +69,7 @@ UNITS = [
     ("mcmc.hip", ["-ffp-contract=off"]),
     ("bilagrid.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("normals.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
+    ("mip.hip", ["-ffp-contract=off"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

@@ -1798,6 +1798,42 @@ int gsr_normal_loss_backward(int H, int W, float tanfovx, float tanfovy, const f
     return GSR_OK;
 }
 
+// ---- 3D smoothing filter of Mip-Splatting (mip.hip) ----
+size_t gsr_mip_filter_scratch_bytes(int P) { return P < 0 ? 0 : GSR_MIP_SCRATCH_BYTES; }
+
+int gsr_mip_filter_3d(int P, const float* means3D, int C, const float* cameras, float* filter_3D, uint8_t* seen, void* scratch, void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (C < 1) return fail(GSR_ERR_INVALID_ARG, "3D filter: at least one camera is needed, got C = " + std::to_string(C));
+    if (P == 0) return GSR_OK;
+    if (!means3D || !cameras || !filter_3D || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only seen may be NULL)");
+    if ((uintptr_t)scratch & 3) return fail(GSR_ERR_INVALID_ARG, "3D filter: scratch must be 4-byte aligned");
+    gsr_launch_mip_filter(P, means3D, C, cameras, filter_3D, seen, (uint32_t*)scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mip_activations(int P, const float* raw_scales, const float* raw_opacity, const float* filter_3D, float* scales_out, float* opacity_out,
+                        void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!raw_scales || !raw_opacity || !filter_3D || !scales_out || !opacity_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    gsr_launch_mip_activations(P, raw_scales, raw_opacity, filter_3D, scales_out, opacity_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mip_activations_backward(int P, const float* raw_scales, const float* raw_opacity, const float* filter_3D, const float* dL_dscales,
+                                 const float* dL_dopacity, float* dL_draw_scales, float* dL_draw_opacity, void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "P < 0");
+    if (P == 0) return GSR_OK;
+    if (!raw_scales || !raw_opacity || !filter_3D || !dL_draw_scales || !dL_draw_opacity)
+        return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only dL_dscales and dL_dopacity may be NULL)");
+    gsr_launch_mip_activations_backward(P, raw_scales, raw_opacity, filter_3D, dL_dscales, dL_dopacity, dL_draw_scales, dL_draw_opacity,
+                                        (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

@@ -487,6 +487,16 @@ void gsr_launch_normal_loss(const GsrNormalsFrame& f, const float* depth, const 
 // dL_dnormals or dL_ddepth may be NULL (both: no launch); each is the same bits whether or not the other is asked for
 void gsr_launch_normal_loss_backward(const GsrNormalsFrame& f, const float* depth, const float* normals, const float* weight,
                                      const float* dL_dloss, float* dL_dnormals, float* dL_ddepth, hipStream_t st);
+// mip.hip: the 3D smoothing filter of Mip-Splatting.  The sweep leaves the largest seen distance and the largest focal length in
+// the two scratch words (cleared on the stream first), the fill kernel behind it turns distances into filter sizes; the activations are one
+// streaming pass each way.  dL_dscales / dL_dopacity may be NULL (a zero gradient, same arithmetic).
+#define GSR_MIP_SCRATCH_BYTES 64
+void gsr_launch_mip_filter(int P, const float* means, int C, const float* cameras /*[C,16]*/, float* filter, uint8_t* seen /*or NULL*/,
+                           uint32_t* words /*[2]*/, hipStream_t st);
+void gsr_launch_mip_activations(int P, const float* raw_scales, const float* raw_opacity, const float* filter, float* scales_out,
+                                float* opacity_out, hipStream_t st);
+void gsr_launch_mip_activations_backward(int P, const float* raw_scales, const float* raw_opacity, const float* filter, const float* dL_dscales,
+                                         const float* dL_dopacity, float* dL_draw_scales, float* dL_draw_opacity, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

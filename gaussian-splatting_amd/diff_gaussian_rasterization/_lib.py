@@ -169,6 +169,10 @@ SIGNATURES = {
     "gsr_normal_loss_partial_count": (C.c_int64, [C.c_int] * 2),
     "gsr_normal_loss": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 6),
     "gsr_normal_loss_backward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float] + [_vp] * 7),
+    "gsr_mip_filter_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "gsr_mip_filter_3d": (C.c_int, [C.c_int, _vp, C.c_int] + [_vp] * 5),
+    "gsr_mip_activations": (C.c_int, [C.c_int] + [_vp] * 6),
+    "gsr_mip_activations_backward": (C.c_int, [C.c_int] + [_vp] * 8),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

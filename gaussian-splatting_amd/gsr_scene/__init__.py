@@ -21,6 +21,7 @@ from plyfile import PlyData, PlyElement
 __all__ = ["gaussian_attribute_names", "save_gaussians_ply", "load_gaussians_ply", "store_points_ply", "fetch_points_ply"]
 # adaptive density control (clone / split / prune as one repack): gsr_scene.densify
 # 3DGS-MCMC density control (cap, relocation, noise): gsr_scene.mcmc
+# 3D smoothing filter of Mip-Splatting (camera sweep, filtered activations): gsr_scene.mip
 
 
 def gaussian_attribute_names(n_rest: int, n_scale: int = 3, n_rot: int = 4):

@@ -746,6 +746,49 @@ int gsr_normal_loss_backward(int H, int W, float tanfovx, float tanfovy, const f
                              const float* dL_dloss, float* dL_dnormals_or_null, float* dL_ddepth_or_null, void* stream);
 
 /*
+ * 3D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024; trained with by Gaussian Opacity Fields and RaDe-GS as well): every Gaussian is
+ * low-passed in world space to the finest sampling rate any training camera sees it at.  The 2D half of the paper is `antialiasing` of the
+ * rasterizer's settings.  gsr_scene/mip.py is the package side.  (Additive, the ABI version stays 4.)
+ *
+ * The camera sweep, upstream's `compute_3D_filter` in one call without a host synchronisation.  means3D is [P,3]; a camera record is 16 floats
+ * (64 bytes), cameras is [C,16]:
+ *   [0..8] R, row-major, and [9..11] T such that cam = xyz R + T (upstream's camera.R, camera.T: cam_j = sum_i xyz_i R[3 i + j] + T[j]);
+ *   [12] focal_x, [13] focal_y, [14] image width W, [15] image height H (as floats).
+ * For each Gaussian, distance = 100000; for each camera with z = cam.z: the camera SEES the Gaussian when z > 0.2 and
+ *   -0.15 W <= cam.x / z focal_x + W / 2 <= 1.15 W,   -0.15 H <= cam.y / z focal_y + H / 2 <= 1.15 H,
+ * and then distance = min(distance, z).  After all cameras a Gaussian that no camera saw takes the largest distance over those that were
+ * seen, and filter_3D[i] = distance / max_c focal_x * sqrt(0.2), the maximum over ALL cameras, those that see nothing included.  seen (uint8
+ * [P], upstream's valid_points) is optional: NULL costs nothing and changes no bit of filter_3D.
+ * The screen test is evaluated as |cam.x focal_x| <= 0.65 W z (the same set for z > 0): a decision within rounding of a threshold may differ
+ * from upstream's division.  Two departures from upstream: (1) when no Gaussian is seen at all, every distance stays 100000 (upstream raises on
+ * the empty max); (2) a mean with a NaN / inf component fails every comparison: it is unseen and takes the fill value, and no other Gaussian's
+ * value changes by a bit (upstream: an inf depth that passes the tests becomes everybody's fill value).  Two runs give the same bits: the
+ * maximum is an integer maximum on the bits of positive floats.  scratch: gsr_mip_filter_scratch_bytes(P) bytes, 4-byte aligned, caller-owned;
+ * its contents need not be initialised.  P == 0 succeeds without a launch; C < 1 is refused.
+ *
+ * The activations that the filter changes, one streaming pass each way; raw_scales [P,3] (log), raw_opacity [P] (logit), filter_3D [P]:
+ *   s_i = exp(raw_scales[i]);   scales_out[i] = s'_i = sqrt(s_i^2 + f^2);   opacity_out = sigmoid(raw_opacity) c_0 c_1 c_2,   c_i = s_i / s'_i
+ * NUMERICS CONTRACT.  The opacity factor is the product of the three per-axis ratios.  Upstream's sqrt(prod s_i^2 / prod (s_i^2 + f^2)) forms
+ * products of six scales, which leave fp32's normal range for scales near 1e-7 (0/0 where both underflow); here nothing smaller than s_i^2 is
+ * ever formed, so every scale down to 1e-18 is handled at full relative accuracy.
+ * The backward takes dL/dscales' [P,3] and / or dL/dopacity' [P] (either may be NULL: a zero gradient, evaluated through the same arithmetic,
+ * so the results are the bits of a call that passes zeros) and writes both dL_draw_scales [P,3] and dL_draw_opacity [P]:
+ *   dL/dr_i = g_i s_i c_i + g_o o' (f / s'_i)^2;      dL/dr_o = g_o c_0 c_1 c_2 sigma (1 - sigma).        filter_3D is a constant (a buffer upstream).
+ * Non-finite rows (they never spread): a row's outputs are what the arithmetic gives for its own inputs -- NaN for a NaN,
+ * inf / NaN for a scale that overflows, the limits for the saturating infinities -- and no other row changes by a bit.  The gradient row (all
+ * four values) is zero whenever a raw value or f of the row is not finite, or one of its four outputs is not.
+ * Pointers that are all 16-byte aligned take 16-byte accesses (four Gaussians per lane); any other alignment computes the same bits.
+ */
+size_t gsr_mip_filter_scratch_bytes(int P);                                  /* 0: P < 0 */
+int gsr_mip_filter_3d(int P, const float* means3D, int C, const float* cameras, float* filter_3D, uint8_t* seen_or_null, void* scratch,
+                      void* stream);
+int gsr_mip_activations(int P, const float* raw_scales, const float* raw_opacity, const float* filter_3D, float* scales_out, float* opacity_out,
+                        void* stream);
+int gsr_mip_activations_backward(int P, const float* raw_scales, const float* raw_opacity, const float* filter_3D,
+                                 const float* dL_dscales_or_null, const float* dL_dopacity_or_null, float* dL_draw_scales,
+                                 float* dL_draw_opacity, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points

@@ -16,7 +16,8 @@ What is mirrored from the reference (train.py:73-190, arguments/__init__.py:72-1
     threshold 0.0002, opacity floor 0.005, screen-size pruning after iteration 3000, opacity reset every 3000 iterations
     (train.py:160-174, arguments/__init__.py:91-95).
 Beyond the reference, off by default: `--bilateral_grid`, gsplat's per-image appearance compensation (fused_bilagrid, INTEGRATION.md 3j);
-`--normal_consistency`, the depth-normal consistency regulariser of 2DGS (gsr_normals).
+`--normal_consistency`, the depth-normal consistency regulariser of 2DGS (gsr_normals); `--mip_filter`, the 3D smoothing
+filter and the antialiased rasterizer of Mip-Splatting (gsr_scene.mip).
 Reported: iterations/s (whole run and per 5000-iteration window), the Gaussian count over time, peak device memory, the
 largest R-sized scratch buffers.  One JSON line on stdout (also written to gpurun_out/train_run.json)."""
 from __future__ import annotations
@@ -70,6 +71,10 @@ def main():
     ap.add_argument("--normal_consistency", type=float, default=0.0, metavar="LAMBDA",
                     help="add LAMBDA * gsr_normals.normal_consistency_loss (2DGS uses 0.05): per-Gaussian normals and the view-space z rendered as "
                          "four feature channels with geometry gradients, depth = D / alpha, weight = the detached alpha; 0 (default) = off")
+    ap.add_argument("--mip_filter", action="store_true",
+                    help="Mip-Splatting: the 3D smoothing filter (gsr_scene.mip.compute_3d_filter over the training cameras at the start, after every "
+                         "density-control step and every 100 iterations afterwards), the activations through gsr_scene.mip.filtered_activations, "
+                         "antialiasing=True in the rasterizer's settings")
     ap.add_argument("--fuse-sh-step", action="store_true",
                     help="opt-in: the optimizer step of f_dc / f_rest is applied by the per-Gaussian backward kernel "
                          "(diff_gaussian_rasterization.fuse_sh_adam_into_backward); switched off on the iterations that densify, "
@@ -109,12 +114,19 @@ def main():
     # the reference's Camera objects keep their matrices on the device (scene/cameras.py): upload once, not per iteration
     _dev_cams = {}
 
-    def settings(cam, deg):
+    def settings(cam, deg, aa=False):
         c = _dev_cams.get(id(cam))
         if c is None:
             c = _dev_cams[id(cam)] = cam.to(dev)
         return GaussianRasterizationSettings(H, W, cam.tanfovx, cam.tanfovy, bg, 1.0, c.world_view_transform, c.full_proj_transform,
-                                             deg, c.camera_center, False, False, False)
+                                             deg, c.camera_center, False, False, aa)
+
+    mip_cams = filter_3D = None
+    if a.mip_filter:      # the camera records once (R = the view matrix's 3 x 3 block, T = its last row; centred principal point)
+        from gsr_scene import mip
+        mip_cams = torch.stack([torch.cat([cam.world_view_transform[:3, :3].reshape(-1), cam.world_view_transform[3, :3],
+                                           torch.tensor([W / (2.0 * cam.tanfovx), H / (2.0 * cam.tanfovy), float(W), float(H)])])
+                                for cam in cams]).to(dev)
 
     with torch.no_grad():
         gts = []
@@ -189,10 +201,16 @@ def main():
         if a.fuse_sh_step:      # (the tensors change at every densification; no fused step where the loop below replaces them)
             set_fusion(not (500 < it < 15000 and it % 100 == 0) and it < a.iters)
         m2 = torch.zeros(P, 3, device=dev, requires_grad=True)
-        S = settings(cams[ci], deg)
-        scales_act, rot_act = torch.exp(params["scaling"]), torch.nn.functional.normalize(params["rotation"])
+        S = settings(cams[ci], deg, a.mip_filter)
+        rot_act = torch.nn.functional.normalize(params["rotation"])
+        if a.mip_filter:
+            if filter_3D is None or (it >= 15000 and it % 100 == 0):      # start, after density control, every 100 once that has ended
+                filter_3D = mip.compute_3d_filter(params["xyz"], mip_cams)
+            scales_act, opacity_act = mip.filtered_activations(params["scaling"], params["opacity"], filter_3D)
+        else:
+            scales_act, opacity_act = torch.exp(params["scaling"]), torch.sigmoid(params["opacity"])
         out = (GaussianRasterizer(S, return_alpha=True) if a.normal_consistency > 0 else GaussianRasterizer(S))(
-            means3D=params["xyz"], means2D=m2, dc=params["f_dc"], shs=params["f_rest"], opacities=torch.sigmoid(params["opacity"]),
+            means3D=params["xyz"], means2D=m2, dc=params["f_dc"], shs=params["f_rest"], opacities=opacity_act,
             scales=scales_act, rotations=rot_act)
         img, radii = out[0], out[1]
         gt = gts[ci]
@@ -214,6 +232,7 @@ def main():
                     grow = params["xyz"].shape[0] < a.max_P
                     params, stats, _ = densify_and_prune(opt, stats, max_grad=a.grad_threshold if grow else 1e30, min_opacity=0.005, extent=ext,
                                                          max_screen_size=20 if it > 3000 else None, radii=radii)
+                    filter_3D = None      # (--mip_filter: recomputed for the new set on the next iteration)
                 if it % 3000 == 0:
                     params["opacity"] = reset_opacity(opt, 0.01)
             if it < a.iters:
@@ -343,7 +362,8 @@ def main():
                                   f"replacement, target scene {a.P_target} Gaussians (SURVEY 8(d) generator, seed {a.seed})",
                       "optimizer": ("FusedAdam (dense)" if a.dense_adam else "SparseGaussianAdam + separate_sh call form") + (" + SH step inside backward (opt-in fusion)" if a.fuse_sh_step else "")
                                    + (" + per-camera bilateral grids 16x16x8 (slice before the loss, 10 tv_loss, FusedAdam lr 2e-3)" if a.bilateral_grid else "")
-                                   + (f" + {a.normal_consistency:g} x depth-normal consistency (gsr_normals on a 4-channel feature render)" if a.normal_consistency > 0 else ""),
+                                   + (f" + {a.normal_consistency:g} x depth-normal consistency (gsr_normals on a 4-channel feature render)" if a.normal_consistency > 0 else "")
+                                   + (" + Mip-Splatting's 3D smoothing filter (gsr_scene.mip) and antialiasing" if a.mip_filter else ""),
                       "schedule": f"densify 500..15000 every 100 (grad {a.grad_threshold:g}, opacity 0.005, size 20 after 3000), opacity reset / 3000, "
                                   "SH degree +1 / 1000, position lr 1.6e-4 -> 1.6e-6 x extent", "extent": ext},
            "final_P": int(params["xyz"].shape[0]), "max_P": max(sizes + [P0]), "P_every_1000_iters": sizes,
