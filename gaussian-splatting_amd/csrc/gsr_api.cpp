@@ -449,6 +449,11 @@ int gsr_set_option(const char* name, int value) {
         gsr_set_ranking_generic(value);
         return GSR_OK;
     }
+    if (!strcmp(name, "ranking_pad_last")) {
+        if (value != 0 && value != 1) return fail(GSR_ERR_INVALID_ARG, "ranking_pad_last must be 1 (partial blocks of the tile sort rank their missing slots as padding of the highest digit) or 0 (per-item validity)");
+        gsr_set_ranking_pad_last(value);
+        return GSR_OK;
+    }
     if (!strcmp(name, "debug_last_ranking_widths")) {      // test hook, changes nothing: succeeds iff the most recent emit_scatter / bucket_scatter launches were
         // instantiated for the bucket digit value >> 4 and the low digit value & 15 (0: the run-time-width kernel)
         if (value < 0 || value > 0x88) return fail(GSR_ERR_INVALID_ARG, "debug_last_ranking_widths: hb << 4 | lb, each 0 (generic) or 5..8");

@@ -266,6 +266,10 @@ void gsr_set_level2_scan_mode(int v);      // tilesort.hip (option level2_scan_m
 // (C++17 inline variable): either file is also compiled on its own (tests/simt).
 inline int g_ranking_generic = 0;
 inline void gsr_set_ranking_generic(int v) { g_ranking_generic = v; }
+// option ranking_pad_last: 1 (default) = emit_scatter / bucket_scatter rank the slots a partial block does not have as padding items of the highest digit,
+// 0 = they carry a validity predicate per item (the earlier form; A/B, tests).  tilesort.hip local_stable_sort
+inline int g_ranking_pad_last = 1;
+inline void gsr_set_ranking_pad_last(int v) { g_ranking_pad_last = v; }
 // TEST HOOK (option debug_last_ranking_widths): the digit widths the most recent emit_scatter / bucket_scatter launches were instantiated for (0: generic, -1: none yet)
 inline int g_ranking_last_hb = -1, g_ranking_last_lb = -1;
 // sort.hip: in-place exclusive scan of every digit row of a [ndigits][nblocks] block-histogram table + row totals

@@ -88,6 +88,14 @@ __device__ __forceinline__ uint32_t div_small24(uint32_t a, uint32_t b, uint32_t
     return q;
 }
 
+// no instruction: the wave-uniform value exists in an SGPR here, so the optimiser does not fold the expression that made it into its consumers
+__device__ __forceinline__ uint32_t pin_sgpr_u32(uint32_t v) {
+#if !defined(GSR_SIMT_SHIM)
+    asm volatile("" : "+s"(v));
+#endif
+    return v;
+}
+
 // 64-bit mask of the lanes whose `digit` (low `bits` bits significant) equals this lane's, among the lanes in `valid_mask`.
 // FOUR VALU instructions per bit: the bit sign-extended by one v_bfe_i32, one v_cmp for the ballot, and "mask & ~(ballot ^ bit)" as one
 // v_bitop3_b32 per half (truth table 0x90 = a & ~(b ^ c)).  The plain form ("mask &= bit ? bal : ~bal") compiles to EIGHT (v_and, two v_cmp,

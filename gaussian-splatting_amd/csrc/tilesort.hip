@@ -31,10 +31,17 @@ using namespace gsrw;
 
 namespace {
 
-// (Both ranking kernels run at four waves per SIMD -- 126 / 107 VGPRs with the run-time digit width when this was measured, 104-110 in the width
-// instantiations of today, profiles/isa_ranking.json -- and spend half of their wave-cycles waiting (SQ_WAIT_ANY).  Forcing five / six
-// with amdgpu_waves_per_eu spills 6-25 registers inside the ranking loops: emission 0.053 -> 0.076 ms, tile sort 0.042 -> 0.051 / 0.059 ms,
-// profiles/r05_ab_ranking_occupancy.json.)
+// (With per-item validity -- ranking_pad_last = 0, the only form until that option existed -- both ranking kernels run at four waves per SIMD: 126 / 107
+// VGPRs with the run-time digit width when this was measured, 104-110 in the width instantiations, profiles/isa_ranking.json; they spend half of their
+// wave-cycles waiting (SQ_WAIT_ANY).  Forcing five / six with amdgpu_waves_per_eu spilled 6-25 registers inside the ranking loops: emission
+// 0.053 -> 0.076 ms, tile sort 0.042 -> 0.051 / 0.059 ms, profiles/r05_ab_ranking_occupancy.json.)
+// Without per-item validity the width instantiations need 90-94 VGPRs and the fifth wave fits by itself, no attribute asked for it.
+// GSR_RANKING_WAVES4, measurement builds only: the same kernels held at four, to tell what the fifth wave is worth from what the removed instructions are.
+#ifdef GSR_RANKING_WAVES4
+#define GSR_RANKING_OCCUPANCY __attribute__((amdgpu_waves_per_eu(4, 4)))
+#else
+#define GSR_RANKING_OCCUPANCY
+#endif
 constexpr int TS_ITEMS = GSR_TS_ITEMS;              // instances per workgroup
 constexpr int TS_IPT = TS_ITEMS / WG_THREADS;       // 16 per thread
 constexpr int TS_MAXBINS = 256;
@@ -64,13 +71,17 @@ template <> struct Pack<uint64_t> {
 // (first slot, rectangle, id) record is staged in LDS with coalesced loads, so the only dependent global round trips of
 // the kernel are table -> staging.
 // Returns in tile[r] the tile id, in id[r] the Gaussian id (WANT_ID), vmask bit r = slot < R.
+// PAD (option ranking_pad_last, local_stable_sort): no vmask -- the caller ranks the slots behind R as padding.  Such a slot (the frame's last block
+// only) is expanded like any other: its owner is the block's last marked Gaussian (the max-scan runs on), a valid record, so a = k - g.x is at most that
+// Gaussian's tile count + TS_ITEMS < 2^18 and every factor of the 24-bit multiplies stays far inside 24 bits; the tile id that comes out lies outside the
+// rectangle, may wrap, and is never used: the caller replaces its digit, and the word is dropped at the final store.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int TS_NGCAP = 1024;      // Gaussians per block whose record is staged in LDS (beyond: global fetch)
 
 // MUL24: the divisions and the row product of the expansion with 24-bit multiplies (mul_u24: one issue slot against four of v_mul_lo_u32, 34 of
 // them per thread).  Holds for the 32-bit-word emission of the fused path: at most TS_MAX_FUSED_TILES tiles, so the instance index inside a
 // rectangle, the rectangle's width, the tile row and gx are all <= 2^16 (static_assert at TS_MAX_FUSED_TILES, checked again by the launcher).
-template <bool WANT_ID, bool MUL24>
+template <bool WANT_ID, bool MUL24, bool PAD>
 __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uint2* __restrict__ block_first,
                                                    const uint32_t* __restrict__ offsets, const uint2* __restrict__ rect_sorted,
                                                    const uint32_t* __restrict__ order, uint16_t* s_own /*[TS_ITEMS]*/,
@@ -126,15 +137,15 @@ __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uin
     __syncthreads();
     const uint32_t s0 = (uint32_t)w * (64u * TS_IPT) + (uint32_t)lane;     // slot of item 0 inside the block
     vmask = 0;
-    auto finish = [&](int r, uint32_t k, const uint4& g) {
+    auto finish = [&](int r, uint32_t k, const uint4& g, const bool clamp) {
         if (WANT_ID) id[r] = g.w;
         const uint32_t minx = g.y & 0xFFFFu, wd = (g.y >> 16) - minx, miny = g.z & 0xFFFFu;
         uint32_t rx;
         if (MUL24) {
-            const uint32_t ry = div_small24((k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
+            const uint32_t ry = div_small24((!clamp || k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
             tile[r] = mul_u24(miny + ry, (uint32_t)gx) + minx + rx;
         } else {
-            const uint32_t ry = div_small((k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
+            const uint32_t ry = div_small((!clamp || k < R ? k : R - 1u) - g.x, wd ? wd : 1u, rx);
             tile[r] = (miny + ry) * (uint32_t)gx + minx + rx;
         }
     };
@@ -148,15 +159,15 @@ __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uin
 #pragma unroll
         for (int r = 0; r < TS_IPT; ++r) {
             const uint32_t k = b0 + s0 + (uint32_t)r * 64u;
-            if (k < R) vmask |= 1u << r;
-            finish(r, k, s_g4[own[r]]);
+            if (!PAD && k < R) vmask |= 1u << r;
+            finish(r, k, s_g4[own[r]], !PAD);
         }
     } else {            // (more than 1024 Gaussians in 4096 instances: fewer than four tiles each)
 #pragma unroll 1
         for (int r = 0; r < TS_IPT; ++r) {
             const uint32_t slot = s0 + (uint32_t)r * 64u;
             const uint32_t k = b0 + slot;
-            if (k < R) vmask |= 1u << r;
+            if (!PAD && k < R) vmask |= 1u << r;
             const uint32_t i = s_own[slot];
             uint4 g;
             if (i < (uint32_t)TS_NGCAP) {
@@ -165,7 +176,7 @@ __device__ __forceinline__ void generate_instances(uint32_t R, int gx, const uin
                 const uint2 rc = rect_sorted[j_lo + i];
                 g = make_uint4(offsets[j_lo + i - 1], rc.x, rc.y, WANT_ID ? order[j_lo + i] : 0u);
             }
-            finish(r, k, g);
+            finish(r, k, g, true);      // (this path keeps the clamp in both forms: it is not the hot one)
         }
     }
 }
@@ -216,7 +227,20 @@ emit_hist(uint32_t R, int gx, int lb, int nb1, const uint2* __restrict__ block_f
 // the items in workgroup-local sorted order (s_word / s_dig) and the global base of every digit (digit_base, already
 // offset so that global position = digit_base[d] + local index).  ranks: wave64 ballot matching, no atomics.
 // BITS > 0: the digit width as a compile-time constant (== bits; match_digit<BITS>), 0: the run-time width.
-template <typename WordT, int BITS>
+//
+// PAD (option ranking_pad_last = 1, the default): the routine knows no validity.  All 4096 slots hold an item; the caller has given the slots that do
+// not exist (emit_scatter: k >= R, bucket_scatter: i >= end) the HIGHEST digit, nbins - 1, and vmask is not read.  That is exact, because
+//   * the padding slots are the highest slots of their block and the ranking is stable in slot order ((wave, r, lane) order IS slot order), so inside
+//     the block they rank behind every real item of the top digit and of every lower digit: in the block-local sorted order they occupy exactly the
+//     indices >= nvalid, and the callers' `i < nvalid` test at the final store drops them;
+//   * the 4096 local positions are a permutation of 0..4095, so the staging writes stay inside s_word / s_dig, and nbins - 1 <= 255 fits s_dig;
+//   * they inflate wave_cnt of the top digit only, and there only behind the last real item: the local base of every digit (an exclusive scan in digit
+//     order) and the per-wave bases in front of a real item are what they were; digit_base comes from the global histograms, which count real items;
+//   * no later block exists whose items they could displace: they sit in the frame's last emission block / in their bucket's last level-2 block.
+// What goes: the vmask bit and its extraction, the ballot of the valid lanes as the match's start mask (the chain starts from the constant full mask),
+// the selects around `prior`, the leader test's second term and the guard of the placement.
+// PAD = false (ranking_pad_last = 0): the per-item validity of the earlier form, kept for the same-library A/B and the tests.
+template <typename WordT, int BITS, bool PAD>
 __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], uint32_t (&digit)[TS_IPT] /*clobbered*/, uint32_t vmask,
                                                   int bits, int nbins, uint32_t my_digit_base /*thread d: global base of digit d*/,
                                                   uint32_t (*wave_cnt)[TS_MAXBINS], uint32_t* digit_base, uint32_t* wsum,
@@ -231,9 +255,9 @@ __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], u
     const uint64_t lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int r = 0; r < TS_IPT; ++r) {
-        const bool valid = (vmask >> r) & 1u;
+        const bool valid = PAD || ((vmask >> r) & 1u);
         const uint32_t d = digit[r];
-        const uint64_t mask = match_digit_w<BITS>(d, bits, __ballot(valid));
+        const uint64_t mask = match_digit_w<BITS>(d, bits, PAD ? ~0ull : __ballot(valid));
         const uint32_t prior = valid ? wave_cnt[w][d] : 0u;
         const uint32_t below = lanes_below(mask, lt_mask);
         // the item's rank among the wave's items of its digit rides in the upper half of the digit word (rank < 4096)
@@ -263,7 +287,7 @@ __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], u
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TS_IPT; ++r) {
-        if ((vmask >> r) & 1u) {
+        if (PAD || ((vmask >> r) & 1u)) {
             const uint32_t d = digit[r] & 0xFFFFu;
             const uint32_t lp = wave_cnt[w][d] + (digit[r] >> 16);
             s_word[lp] = word[r];
@@ -274,9 +298,9 @@ __device__ __forceinline__ void local_stable_sort(const WordT (&word)[TS_IPT], u
 }
 
 // level 1 scatter (+ first-emission indices for the backward, + the bucket tables of level 2 from block 0)
-// HB > 0: the bucket digit's width as a compile-time constant (== hb), 0: the generic kernel.  MUL24: generate_instances
-template <typename WordT, int HB, bool MUL24>
-__global__ void __launch_bounds__(WG_THREADS)
+// HB > 0: the bucket digit's width as a compile-time constant (== hb), 0: the generic kernel.  MUL24: generate_instances.  PAD: local_stable_sort
+template <typename WordT, int HB, bool MUL24, bool PAD>
+__global__ void __launch_bounds__(WG_THREADS) GSR_RANKING_OCCUPANCY
 emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block_first, const uint32_t* __restrict__ offsets,
              const uint2* __restrict__ rect_sorted, const uint32_t* __restrict__ order, const uint32_t* __restrict__ hist,
              const uint32_t* __restrict__ digit_total, int nblk, WordT* __restrict__ words_out,
@@ -301,8 +325,8 @@ emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block
     // independent of everything else: requested first
     const uint32_t my_total = tid < nb1 ? digit_total[tid] : 0u;
     const uint32_t my_hist = tid < nb1 ? hist[(int64_t)tid * nblk + blockIdx.x] : 0u;
-    uint32_t tile[TS_IPT], id[TS_IPT], vmask;
-    generate_instances<true, MUL24>(R, gx, block_first, offsets, rect_sorted, order, s_own, s_g4, wsum, splats, tile, id, vmask);
+    uint32_t tile[TS_IPT], id[TS_IPT], vmask = 0;
+    generate_instances<true, MUL24, PAD>(R, gx, block_first, offsets, rect_sorted, order, s_own, s_g4, wsum, splats, tile, id, vmask);
     // global base of bucket d for this block = exclusive scan of the bucket totals + instances of earlier blocks
     uint32_t tot[1] = {my_total};
     const uint32_t bbase = block_excl_scan<1>(tot, wsum, lane, w);
@@ -323,15 +347,28 @@ emit_scatter(uint32_t R, int gx, int lb, int hb, const uint2* __restrict__ block
     WordT word[TS_IPT];
     uint32_t digit[TS_IPT];
     const uint32_t lomask = (1u << lb) - 1u;
+    if (PAD) {      // a slot behind R (the frame's last block only): the top bucket's digit; its word is never stored
+        // (the mask as an opaque scalar: v_and + v_lshl_or per item as in the other form, where the compiler otherwise rewrites it as ~(-1 << lb) and folds
+        // that into v_bitop3_b32 of the same cost -- every v_bitop3_b32 of this kernel stays one of the match chain's, which is what tools/isa_audit.py counts)
+        const uint32_t lomask_pad = pin_sgpr_u32(lomask);
+        const uint32_t k0 = blockIdx.x * (uint32_t)TS_ITEMS + (uint32_t)w * (64u * TS_IPT) + (uint32_t)lane;
 #pragma unroll
-    for (int r = 0; r < TS_IPT; ++r) {
-        const bool valid = (vmask >> r) & 1u;
-        word[r] = Pack<WordT>::make(valid ? id[r] : 0u, tile[r] & lomask, lb);
-        digit[r] = valid ? (tile[r] >> lb) : 0u;
+        for (int r = 0; r < TS_IPT; ++r) {
+            word[r] = Pack<WordT>::make(id[r], tile[r] & lomask_pad, lb);
+            const uint32_t d = tile[r] >> lb;
+            digit[r] = k0 + (uint32_t)r * 64u < R ? d : (uint32_t)nb1 - 1u;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < TS_IPT; ++r) {
+            const bool valid = (vmask >> r) & 1u;
+            word[r] = Pack<WordT>::make(valid ? id[r] : 0u, tile[r] & lomask, lb);
+            digit[r] = valid ? (tile[r] >> lb) : 0u;
+        }
     }
     // (the barriers at the top of local_stable_sort separate the last read of the generation arrays from the first write
     // of the word staging that shares their LDS)
-    local_stable_sort<WordT, HB>(word, digit, vmask, hb, nb1, bbase + my_hist, wave_cnt, digit_base, wsum, s_word, s_dig);
+    local_stable_sort<WordT, HB, PAD>(word, digit, vmask, hb, nb1, bbase + my_hist, wave_cnt, digit_base, wsum, s_word, s_dig);
     const uint32_t b0 = blockIdx.x * (uint32_t)TS_ITEMS;
     const uint32_t nvalid = R - b0 < (uint32_t)TS_ITEMS ? R - b0 : (uint32_t)TS_ITEMS;
 #pragma unroll
@@ -456,9 +493,13 @@ bucket_scan(int lb, int h0, int n_tiles, const uint32_t* __restrict__ bucket_bas
 // digit, the counts of its bucket's workgroups (all of them: the per-tile bases; those before it: its own offsets) in one round
 // of independent loads.  The bucket's first workgroup writes the tile ranges.  Chosen by the host while a bucket has few
 // workgroups (the slab a workgroup reads is workgroups-per-bucket x nb2 x 4 bytes).
-// LB > 0: the low digit's width as a compile-time constant (== lb), 0: the generic kernel
-template <typename WordT, bool FUSED_SCAN, int LB>
-__global__ void __launch_bounds__(WG_THREADS)
+// LB > 0: the low digit's width as a compile-time constant (== lb), 0: the generic kernel.  PAD: local_stable_sort -- a slot behind `end` (the
+// bucket's last workgroup only) reads as the word "id 0, low digit all ones", the bucket's top digit, instead of carrying a valid bit.
+// (Tried on top of it and not kept: the sixteen loads as range-checked raw buffer loads at immediate offsets, a slot behind `end` reading 0 -- 41 VALU,
+// 30 SALU and 18 branches fewer per thread, and the kernel's median did not move: 25.6 -> 25.7 us, profiles/ab_ranking_padding.json.  The kernel no
+// longer waits on issue slots.)
+template <typename WordT, bool FUSED_SCAN, int LB, bool PAD>
+__global__ void __launch_bounds__(WG_THREADS) GSR_RANKING_OCCUPANCY
 bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, const uint32_t* __restrict__ bucket_base,
                const uint32_t* __restrict__ blk2_start, const uint32_t* __restrict__ hist2,
                const uint32_t* __restrict__ tile_base, uint32_t* __restrict__ point_list, uint2* __restrict__ ranges, int n_tiles) {
@@ -480,10 +521,10 @@ bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, 
     for (int r = 0; r < TS_IPT; ++r) {
         const uint32_t i = wbase + (uint32_t)r * 64u;
         const bool valid = i < end;
-        const WordT wd = valid ? words[i] : (WordT)0;
+        const WordT wd = valid ? words[i] : (WordT)(PAD ? lomask : 0u);
         id[r] = Pack<WordT>::id(wd, lb);
         digit[r] = Pack<WordT>::lo(wd, lomask);
-        if (valid) vmask |= 1u << r;
+        if (!PAD && valid) vmask |= 1u << r;
     }
     uint32_t my_base = 0u;
     if (FUSED_SCAN) {
@@ -530,7 +571,7 @@ bucket_scatter(int lb, int hb, int h0, int h1, const WordT* __restrict__ words, 
     } else {
         my_base = tid < nb2 ? tile_base[h * (uint32_t)nb2 + tid] + hist2[(int64_t)B2 * nb2 + tid] : 0u;
     }
-    local_stable_sort<uint32_t, LB>(id, digit, vmask, lb, nb2, my_base, wave_cnt, digit_base, wsum, s_id, s_dig);
+    local_stable_sort<uint32_t, LB, PAD>(id, digit, vmask, lb, nb2, my_base, wave_cnt, digit_base, wsum, s_id, s_dig);
     const uint32_t nvalid = end - begin;
 #pragma unroll
     for (int r = 0; r < TS_IPT; ++r) {
@@ -582,9 +623,11 @@ void gsr_launch_tile_sort_level1(const GsrTileSortPlan& plan, int64_t R, int gx,
     hipLaunchKernelGGL(emit_hist, dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, nb1, block_first, offsets, rect_sorted,
                        hist1, nblk);
     gsr_launch_rs_scan(hist1, nblk, nb1, digit_total, st);
+#define GSR_L1_SCATTER_P(WORD_, HB_, MUL24_, PAD_)                                                                                                  \
+    hipLaunchKernelGGL((emit_scatter<WORD_, HB_, MUL24_, PAD_>), dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, plan.hb, block_first,      \
+                       offsets, rect_sorted, order, hist1, digit_total, nblk, (WORD_*)words, bucket_base, blk2_start, splats)
 #define GSR_L1_SCATTER(WORD_, HB_, MUL24_)                                                                                                          \
-    hipLaunchKernelGGL((emit_scatter<WORD_, HB_, MUL24_>), dim3(nblk), dim3(WG_THREADS), 0, st, R32, gx, plan.lb, plan.hb, block_first, offsets,   \
-                       rect_sorted, order, hist1, digit_total, nblk, (WORD_*)words, bucket_base, blk2_start, splats)
+    do { if (g_ranking_pad_last) GSR_L1_SCATTER_P(WORD_, HB_, MUL24_, true); else GSR_L1_SCATTER_P(WORD_, HB_, MUL24_, false); } while (0)
     // The 24-bit multiplies of the expansion need the fused path's tile bound (every factor <= the tile count <= 2^16): a plan of at most 16 tile-id
     // bits says so.  The 64-bit-word kernel, and any caller outside that bound, keep the full multiplies.
     const bool mul24 = plan.fused && plan.lb + plan.hb <= 16 && gx <= TS_MAX_FUSED_TILES;
@@ -600,6 +643,7 @@ void gsr_launch_tile_sort_level1(const GsrTileSortPlan& plan, int64_t R, int gx,
         default: GSR_L1_SCATTER(uint32_t, 0, true); break;
     }
 #undef GSR_L1_SCATTER
+#undef GSR_L1_SCATTER_P
 }
 
 int g_level2_scan_mode = 0;      // option level2_scan_mode: 0 = automatic, 1 = separate bucket_scan launch, 2 = folded into bucket_scatter
@@ -630,9 +674,11 @@ void gsr_launch_tile_sort_level2(const GsrTileSortPlan& plan, int64_t R, int n_t
     if (!fused)
         hipLaunchKernelGGL(bucket_scan, dim3(h1 - h0), dim3(WG_THREADS), 0, st, plan.lb, h0, n_tiles, bucket_base, blk2_start, hist2, tile_base,
                            ranges);
-#define GSR_L2_SCATTER(WORD_, FUSED_, LB_)                                                                                              \
-    hipLaunchKernelGGL((bucket_scatter<WORD_, FUSED_, LB_>), dim3(nblk2), dim3(WG_THREADS), 0, st, plan.lb, plan.hb, h0, h1, (const WORD_*)words,  \
-                       bucket_base, blk2_start, hist2, tile_base, point_list, ranges, n_tiles)
+#define GSR_L2_SCATTER_P(WORD_, FUSED_, LB_, PAD_)                                                                                                  \
+    hipLaunchKernelGGL((bucket_scatter<WORD_, FUSED_, LB_, PAD_>), dim3(nblk2), dim3(WG_THREADS), 0, st, plan.lb, plan.hb, h0, h1,                 \
+                       (const WORD_*)words, bucket_base, blk2_start, hist2, tile_base, point_list, ranges, n_tiles)
+#define GSR_L2_SCATTER(WORD_, FUSED_, LB_)                                                                                                          \
+    do { if (g_ranking_pad_last) GSR_L2_SCATTER_P(WORD_, FUSED_, LB_, true); else GSR_L2_SCATTER_P(WORD_, FUSED_, LB_, false); } while (0)
 #define GSR_L2_SCATTER_W(FUSED_)                                                                                                            \
     switch (lb_inst) {      /* the low digit's width of real frames has an instantiation of its own */                                    \
         case 5: GSR_L2_SCATTER(uint32_t, FUSED_, 5); break;                                                                                 \
@@ -648,4 +694,5 @@ void gsr_launch_tile_sort_level2(const GsrTileSortPlan& plan, int64_t R, int n_t
     else { GSR_L2_SCATTER_W(false) }
 #undef GSR_L2_SCATTER_W
 #undef GSR_L2_SCATTER
+#undef GSR_L2_SCATTER_P
 }

@@ -924,6 +924,9 @@ int gsr_profile_trace(uint64_t* out, int max_waves);
  *   ranking_generic  0 (default) = the stable-ranking kernels of the binning chain (emit_scatter, bucket_scatter, ds_segsort) run the
  *                    instantiation compiled for the frame's digit width (tile-id halves of 5..8 bits, bucket digit 5..7: 640x360 up to 4K), 1 = always the
  *                    run-time-width one (A/B and tests; the same bits either way)
+ *   ranking_pad_last 1 (default) = emit_scatter and bucket_scatter rank the slots that a partial block lacks as ordinary items of the highest digit,
+ *                    which the stable ranking leaves behind every real item and the final store drops, 0 = every item carries a validity predicate
+ *                    through the ranking (the earlier form; A/B and tests; the same bits either way)
  * Test hook: debug_last_preprocess_path = 1 (generic) / 2 (hot) changes nothing and succeeds iff the most recent forward took that instantiation.
  * Test hook: debug_last_ranking_widths = hb << 4 | lb changes nothing and succeeds iff the most recent tile sort ran emit_scatter instantiated for
  * hb bits and bucket_scatter for lb bits (0: the run-time-width kernel).

@@ -210,8 +210,15 @@ def ranking(source_dir=None, extra=()):
             occ = re.search(r"; Occupancy:\s*(\d+)", trailer)
             # the truth tables of the kernel's v_bitop3_b32: 0x90 = a & ~(b ^ c) is match_digit's; the compiler forms others from plain and / or / xor
             tables = [x.lower() for x in re.findall(r"^\s+v_bitop3_b32\s.*?bitop3:(0x[0-9a-fA-F]+)", body, re.M)]
+            inst, pad_last = kernel + _template_args(name, kernel), None
+            if unit == "tilesort.hip" and inst.count(",") == 3:
+                # the fourth argument is PAD (option ranking_pad_last): the default form keeps the three-argument name it had before the option existed
+                # (the parent's rows and the tests name it so), the per-item-validity form is marked
+                inst, pad = inst[:-1].rsplit(", ", 1)
+                pad_last = int(pad == "true")
+                inst += ">" if pad_last else "> pad_last=0"
             rows.append({
-                "unit": unit, "kernel": kernel, "instantiation": kernel + _template_args(name, kernel), "symbol": name,
+                "unit": unit, "kernel": kernel, "instantiation": inst, "symbol": name, "pad_last": pad_last,
                 "valu": sum(o.startswith("v_") for o in ops), "salu": sum(o.startswith("s_") and o not in ("s_waitcnt", "s_nop") for o in ops),
                 "v_mov_b32": sum(o.startswith("v_mov_b32") for o in ops), "v_mul_lo_u32": sum(o.startswith("v_mul_lo_u32") for o in ops),
                 "v_mul_u32_u24": sum(o.startswith(("v_mul_u32_u24", "v_mad_u32_u24")) for o in ops),
