@@ -8,54 +8,32 @@
 //
 // Two kernels here, NO atomics, every sum in a fixed association order -> two runs give the same bits:
 //
-//  absgrad_reduce        the structure of contrib_reduce (contrib.hip).  In emission (= depth) order a Gaussian's instances are contiguous.  One wave
-//                        per 64 consecutive Gaussians of the depth order streams their instances 64 at a time (lane = instance: coalesced flag words one
-//                        chunk ahead, then only the third float4 of the flagged slot records, the up to GSR_BWD_SLOTS of an instance added in slot
-//                        order), parks the per-instance pair in LDS, and every Gaussian lane adds its own instances of the chunk in ascending
-//                        (emission) order.  A chunk that belongs to one Gaussian entirely is folded by a butterfly instead -- which chunks those are
-//                        depends on the frame only.  A chunk without a flag is skipped.  The finished pair times 1 / log2(e) goes to words 10, 11 of
-//                        splat_grads[g] (pixel units, like words 0, 1); rows of Gaussians without instances keep the zeros of the launcher of
-//                        bwd_reduce_units, after which this kernel runs on the same stream.  The unit-based reduce chain is not touched.
+//  absgrad_reduce        the instance-run reduce of gsr_reduce.h (reduce_instance_runs, described there with its known cost) over AbsgradOps: only the
+//                        third float4 of the flagged slot records is read, the up to GSR_BWD_SLOTS of an instance added in slot order.  The finished
+//                        pair times 1 / log2(e) goes to words 10, 11 of splat_grads[g] (pixel units, like words 0, 1); rows of Gaussians without
+//                        instances keep the zeros of the launcher of bwd_reduce_units, after which this kernel runs on the same stream.  The
+//                        unit-based reduce chain is not touched.
 //  absgrad_from_records  element-wise: means2D_abs[g] = (0.5 W abs_x, 0.5 H abs_y, 0), the units and layout of dL_dmeans2D.
-// Known cost: a wave of the reduce whose 64 Gaussians hold one very large splat streams all its chunks alone (the tail the blend backward's
-// unit-based reduce was built to avoid); chunks without flags -- most of such a splat -- cost one coalesced flag read each.
 #include "gsr_internal.h"
+#include "gsr_reduce.h"
 
 namespace {
 
 constexpr float LN2 = 0.6931471805599453f;      // 1 / log2(e): the walk's sums are in log2 units (gsr_blend.h conic_*_to_log2)
 
-__global__ void __launch_bounds__(64)
-absgrad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets,
-               const float4* __restrict__ inst_grads /*[GSR_BWD_SLOTS][R] records of 3 float4*/, const uint32_t* __restrict__ flags,
-               float* __restrict__ splat_grads /*[P,12]*/) {
-    __shared__ float s_x[64];
-    __shared__ float s_y[64];
-    const int lane = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.x * 64 + lane;
-    const int64_t jc = j < P ? j : (int64_t)P - 1;
-    const uint32_t incl = offsets[jc];
-    uint32_t excl = jc > 0 ? offsets[jc - 1] : 0u;
-    if (j >= P) excl = incl;                      // (lanes past the last Gaussian own nothing)
-    const uint32_t g = order[jc];
-    const uint32_t c_begin = (uint32_t)__builtin_amdgcn_readlane((int)excl, 0);
-    const uint32_t c_end = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+// what absgrad_reduce does with an instance (gsr_reduce.h reduce_instance_runs): words 10, 11 of the records of its half tiles
+struct AbsgradOps {
+    typedef float2 Value;
+    const float4* __restrict__ inst_grads;
+    int64_t R;
+    float* s_x; float* s_y;      // LDS, 64 each
     float acc_x = 0.0f, acc_y = 0.0f;
-    auto load_flags = [&](uint32_t c) -> uint32_t {
-        const int64_t k = (int64_t)c + lane;
-        return (c < c_end && k < (int64_t)c_end) ? flags[k] : 0u;
-    };
-    uint32_t f_next = load_flags(c_begin);
-    for (uint32_t c = c_begin; c < c_end; c += 64) {
-        const uint32_t f = f_next;
-        f_next = load_flags(c + 64);
-        if (__ballot(f != 0u) == 0ull) continue;      // nobody took these 64 instances (hidden behind nearer ones)
-        const int64_t k = (int64_t)c + lane;
+    __device__ __forceinline__ Value load(uint32_t f, int64_t k) const {
         float4 rec[GSR_BWD_SLOTS];
 #pragma unroll
         for (int q = 0; q < GSR_BWD_SLOTS; ++q) {
             rec[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((f >> (8 * q)) & 0xFFu) rec[q] = inst_grads[((int64_t)q * R + k) * 3 + 2];
+            if ((f >> (8 * q)) & 0xFFu) rec[q] = inst_grads[((int64_t)q * R + k) * 3 + 2];      // (only the third float4 of a record)
         }
         float x = rec[0].z, y = rec[0].w;
 #pragma unroll
@@ -63,28 +41,31 @@ absgrad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint3
             x += rec[q].z;
             y += rec[q].w;
         }
-        // a chunk inside one Gaussian's run: butterfly (the same total in every lane); else the owners add their instances in order
-        const uint32_t lo = max(excl, c), hi = min(incl, c + 64u);
-        const bool own_all = lo < hi && hi - lo == 64u;
-        if (__ballot(own_all) != 0ull) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                x += __shfl_xor(x, off, 64);
-                y += __shfl_xor(y, off, 64);
-            }
-            if (own_all) { acc_x += x; acc_y += y; }
-            continue;
-        }
-        s_x[lane] = x; s_y[lane] = y;
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t i = lo; i < hi; ++i) {
-            acc_x += s_x[i - c];
-            acc_y += s_y[i - c];
-        }
-        __builtin_amdgcn_wave_barrier();
+        return make_float2(x, y);
     }
-    if (j < P && incl > excl)
-        *reinterpret_cast<float2*>(splat_grads + (int64_t)g * 12 + 10) = make_float2(LN2 * acc_x, LN2 * acc_y);
+    __device__ __forceinline__ void fold_take(Value v, bool own_all) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            v.x += __shfl_xor(v.x, off, 64);
+            v.y += __shfl_xor(v.y, off, 64);
+        }
+        if (own_all) take(v);
+    }
+    __device__ __forceinline__ void take(const Value& v) { acc_x += v.x; acc_y += v.y; }
+    __device__ __forceinline__ void park(int lane, const Value& v) const { s_x[lane] = v.x; s_y[lane] = v.y; }
+    __device__ __forceinline__ Value parked(uint32_t i) const { return make_float2(s_x[i], s_y[i]); }
+};
+
+__global__ void __launch_bounds__(64)
+absgrad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets,
+               const float4* __restrict__ inst_grads /*[GSR_BWD_SLOTS][R] records of 3 float4*/, const uint32_t* __restrict__ flags,
+               float* __restrict__ splat_grads /*[P,12]*/) {
+    __shared__ float s_x[64];
+    __shared__ float s_y[64];
+    AbsgradOps ops{inst_grads, R, s_x, s_y};
+    gsrw::reduce_instance_runs(P, order, offsets, flags, ops, [&](uint32_t g) {
+        *reinterpret_cast<float2*>(splat_grads + (int64_t)g * 12 + 10) = make_float2(LN2 * ops.acc_x, LN2 * ops.acc_y);
+    });
 }
 
 __global__ void __launch_bounds__(256)

@@ -19,6 +19,7 @@
 // one-workgroup kernel adds them in index order.
 #include "gsr_internal.h"
 #include "gsr_wave.h"
+#include "gsr_reduce.h"
 
 namespace {
 
@@ -238,18 +239,6 @@ bilagrid_reduce_kernel(GsrBilagridPlan p, const float* __restrict__ scratch, flo
 }
 
 // ---- total variation --------------------------------------------------------------------------------------------------------------------------
-// sum over the 256 threads in a fixed order (a tree over LDS); the total in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    const int tid = (int)threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) s[tid] += s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 struct BgTv { int L, Gh, Gw; double cL, cH, cW; };      // c = 1 / (N * elements of the axis' difference tensor per grid)
 
 __global__ void __launch_bounds__(256)
@@ -267,17 +256,14 @@ bilagrid_tv_kernel(int64_t total, BgTv a, const float* __restrict__ X, double* _
         acc += dy * dy * a.cH;
         acc += dz * dz * a.cL;
     }
-    const double sum = block_sum_f64(acc, s);
+    const double sum = gsrw::block_sum_f64(acc, s);
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 __global__ void __launch_bounds__(256)
 bilagrid_tv_sum_kernel(int n, const double* __restrict__ partials, float* __restrict__ tv_out) {
     __shared__ double s[256];
-    double acc = 0.0;
-    for (int i = (int)threadIdx.x; i < n; i += 256) acc += partials[i];
-    const double sum = block_sum_f64(acc, s);
-    if (threadIdx.x == 0) tv_out[0] = (float)sum;
+    gsrw::block_sum_partials_f64(n, partials, 1.0, tv_out, s);
 }
 
 __global__ void __launch_bounds__(256)

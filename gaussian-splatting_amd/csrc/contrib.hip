@@ -18,15 +18,11 @@
 //                   the instance's emission index k = goffset + (ty - miny) * w + (tx - minx) (4th quad of the splat record) with plain stores --
 //                   a (block, entry) pair is visited once -- plus one flag byte: slots[quad][k], flags[k] byte `quad`.  The launcher clears
 //                   the flags (4 R bytes); slots without a flag are never read.
-//  contrib_reduce   in emission (= depth) order a Gaussian's instances are contiguous.  One wave per 64 consecutive Gaussians of the depth
-//                   order streams their instances 64 at a time (lane = instance: coalesced flag words one chunk ahead, then only the flagged
-//                   slot records, the up to four of an instance combined in slot order), parks the per-instance values in LDS, and every
-//                   Gaussian lane adds its own instances of the chunk in ascending order.  A chunk that belongs to one Gaussian entirely
-//                   (a splat over hundreds of tiles) is folded by a butterfly instead -- which chunks those are depends on the frame only.
-//                   A chunk without a flag is skipped.  Finally `accumulate` and the scattered row stores; rows of Gaussians without
-//                   instances are not touched (the launcher zeroes the arrays when accumulate == 0).
-// Known cost: a wave of the reduce whose 64 Gaussians hold one very large splat streams all its chunks alone (the tail the blend
-// backward's unit-based reduce was built to avoid); chunks without flags -- most of such a splat -- cost one coalesced flag read each.
+//  contrib_reduce   the instance-run reduce that gsr_reduce.h describes (one wave per 64 consecutive Gaussians of the depth order, the ordered path,
+//                   the fold of a chunk owned by one Gaussian, the skipped chunks, its known cost), written out here (see the kernel): the up to
+//                   four slot records of an instance combined in slot order, (sum, max, count) per instance.  Then `accumulate` and the
+//                   scattered row stores; rows of Gaussians without instances are not touched (the launcher zeroes the arrays when
+//                   accumulate == 0).
 #include "gsr_internal.h"
 #include "gsr_blend.h"
 #include "gsr_wave.h"
@@ -132,6 +128,8 @@ contrib_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ranges, 
     }
 }
 
+// (Written out, not gsr_reduce.h's reduce_instance_runs over an ops struct: that form compiled to another schedule of this kernel -- two more s_waitcnt --
+// and measured 0.5 - 1 % slower statistics on the MI355X, twice.  The frame below is that header's, line by line: change them together.)
 __global__ void __launch_bounds__(64)
 contrib_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets, const float4* __restrict__ slots,
                const uint32_t* __restrict__ flags, float* __restrict__ weight_sum, float* __restrict__ weight_max,
@@ -205,12 +203,12 @@ contrib_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint3
 
 }  // namespace
 
-GsrContribScratch gsr_carve_contrib(char* base, int64_t R) {
+GsrContribScratch gsr_carve_slots(char* base, int64_t R, int nb) {
     GsrContribScratch w;
     const size_t r = (size_t)(R > 0 ? R : 0);
     size_t off = 0;
     w.slots = reinterpret_cast<float4*>(base + off);
-    off += gsr_align128(r * 4 * sizeof(float4));
+    off += gsr_align128(r * 4 * (size_t)nb * sizeof(float4));
     w.flags = reinterpret_cast<uint32_t*>(base + off);
     off += gsr_align128(r * sizeof(uint32_t));
     w.bytes = off;
@@ -220,10 +218,10 @@ GsrContribScratch gsr_carve_contrib(char* base, int64_t R) {
 void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* pixel_weight,
                                    const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count, int accumulate,
                                    hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     if (n_band_tiles <= 0 || P <= 0 || R <= 0) return;
     (void)hipMemsetAsync(w.flags, 0, (size_t)R * 4, st);
-    const int groups = (n_band_tiles + 7) / 8;
+    const int groups = gsr_tile_groups(n_band_tiles, 8);
     hipLaunchKernelGGL(contrib_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib,
                        pixel_weight, w.slots, reinterpret_cast<uint8_t*>(w.flags), R);
     hipLaunchKernelGGL(contrib_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, R, f.order, f.offsets, (const float4*)w.slots,

@@ -327,16 +327,16 @@ void gsr_launch_distortion_defaults(const GsrCamDev& cam, float* distortion, flo
 }
 
 void gsr_launch_distortion(const GsrCamDev& cam, const GsrSavedFrame& f, float* distortion, float* saved, int depth_mode, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     if (n_band_tiles <= 0) return;
-    const int groups = (n_band_tiles + 7) / 8;
+    const int groups = gsr_tile_groups(n_band_tiles, 8);
     hipLaunchKernelGGL(distortion_map, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib, distortion,
                        saved, depth_mode);
 }
 
 void gsr_launch_distortion_walk(const GsrCamDev& cam, int64_t R, const GsrSavedFrame& f, int order_mode, const float* dL_ddistortion, const float* saved,
                                 int depth_mode, float* inst_grads, uint32_t* inst_flag, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     // instances that contributed nowhere get no record: only their flag words are cleared -- in the plan kernel's launch, or with a fill
     if (n_band_tiles <= 0) {
         (void)hipMemsetAsync(inst_flag, 0, (size_t)R * 4, st);
@@ -344,7 +344,7 @@ void gsr_launch_distortion_walk(const GsrCamDev& cam, int64_t R, const GsrSavedF
     }
     const uint32_t* tile_order = gsr_launch_bwd_plan(cam, f.block_steps, order_mode ? f.tile_order : nullptr, inst_flag, R, order_mode, st) ? f.tile_order : nullptr;
     const int wave_order = (tile_order && order_mode == 3) ? 1 : 0;
-    const int groups16 = (n_band_tiles + 15) / 16;
+    const int groups16 = gsr_tile_groups(n_band_tiles, 16);
     hipLaunchKernelGGL(distortion_walk, dim3(groups16 * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.final_T, f.n_contrib,
                        dL_ddistortion, saved, depth_mode, reinterpret_cast<float4*>(inst_grads), reinterpret_cast<uint8_t*>(inst_flag), R, tile_order,
                        wave_order);

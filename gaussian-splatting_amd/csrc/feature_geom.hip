@@ -286,7 +286,7 @@ int geom_group_nq(int remaining) {
 
 void gsr_launch_feature_geometry_walks(const GsrCamDev& cam, int64_t R, const GsrSavedFrame& f, int order_mode, const float* features,
                                        const float* dL_dout, int C, float* inst_grads, uint32_t* inst_flag, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     // instances that contributed nowhere get no record: only their flag words are cleared -- in the plan kernel's launch, or with a fill.  The plan
     // (the blend backward's: the cost of a half tile is the forward's count of the entries it blended) serves every group of the call.
     if (n_band_tiles <= 0) {
@@ -295,7 +295,7 @@ void gsr_launch_feature_geometry_walks(const GsrCamDev& cam, int64_t R, const Gs
     }
     const uint32_t* tile_order = gsr_launch_bwd_plan(cam, f.block_steps, order_mode ? f.tile_order : nullptr, inst_flag, R, order_mode, st) ? f.tile_order : nullptr;
     const int wave_order = (tile_order && order_mode == 3) ? 1 : 0;
-    const int groups16 = (n_band_tiles + 15) / 16;
+    const int groups16 = gsr_tile_groups(n_band_tiles, 16);
     const bool vec4 = (C % 4 == 0) && (((uintptr_t)features) & 15) == 0;
     for (int c0 = 0; c0 < C;) {
         const int nq = geom_group_nq(C - c0);

@@ -32,12 +32,13 @@
 //                        order wherever it sits, so the grouping does not show in the bits).  After the batch the Gaussian lanes store the touched
 //                        entries' records (NB float4) to slots[quad][k], k = gsrb::emission_index, plus the flag byte: contrib.hip's scratch shape
 //                        with a wider record ((64 NB + 4) R bytes, NB that of the call's first group), reused by every group of a call.
-//  feature_grad_reduce   contrib_reduce's: one wave per 64 consecutive Gaussians of the depth order, flag words one chunk ahead, only flagged slots read,
-//                        slots in slot order, instances in emission order, a butterfly for a chunk owned by one Gaussian; stores
-//                        dL_dfeatures[g, c0 .. c0 + 4 NB).  Rows of Gaussians without instances keep the launcher's zeros.
+//  feature_grad_reduce   the instance-run reduce of gsr_reduce.h (reduce_instance_runs) over FeatureGradOps: FEAT_NB float4 per instance, slots in slot
+//                        order; stores dL_dfeatures[g, c0 .. c0 + 4 NB).  Rows of Gaussians without instances keep the launcher's zeros.
+//                        (NB = 2 keeps the frame written out as a specialisation, see there: on the shared frame it compiled to another schedule.)
 #include "gsr_internal.h"
 #include "gsr_blend.h"
 #include "gsr_wave.h"
+#include "gsr_reduce.h"
 
 #ifndef GSR_FEAT_G
 #define GSR_FEAT_G 16      // channels per forward walk (a multiple of 4); chosen by measurement, DESIGN.md 5.6
@@ -317,10 +318,69 @@ feature_grad_walk(GsrCamDev cam, int n_band_tiles, const uint2* __restrict__ ran
 
 __device__ __forceinline__ float4 add4(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
+// what feature_grad_reduce does with an instance (gsr_reduce.h reduce_instance_runs): the FEAT_NB float4 of channel sums of its up to four blocks
 template <int FEAT_NB>
-__global__ void __launch_bounds__(64)
-feature_grad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets, const float4* __restrict__ slots,
-                    const uint32_t* __restrict__ flags, float* __restrict__ dL_dfeatures /*[P,C]*/, int C, int c0) {
+struct FeatureGradOps {
+    struct Value { float4 s[FEAT_NB]; };
+    const float4* __restrict__ slots;
+    int64_t R;
+    float4* s_sum;      // LDS, 64 FEAT_NB
+    float4 acc[FEAT_NB];
+    __device__ __forceinline__ FeatureGradOps(const float4* slots_, int64_t R_, float4* s_sum_) : slots(slots_), R(R_), s_sum(s_sum_) {
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) acc[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ Value load(uint32_t f, int64_t k) const {
+        Value v;
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) {
+            float4 rec[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                rec[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if ((f >> (8 * q)) & 0xFFu) rec[q] = slots[((int64_t)q * R + k) * FEAT_NB + h];
+            }
+            v.s[h] = rec[0];
+#pragma unroll
+            for (int q = 1; q < 4; ++q) v.s[h] = add4(v.s[h], rec[q]);      // the up to four blocks of the instance's tile, in slot order (a missing slot adds zeros)
+        }
+        return v;
+    }
+    __device__ __forceinline__ void fold_take(Value v, bool own_all) {
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                v.s[h].x += __shfl_xor(v.s[h].x, off, 64);
+                v.s[h].y += __shfl_xor(v.s[h].y, off, 64);
+                v.s[h].z += __shfl_xor(v.s[h].z, off, 64);
+                v.s[h].w += __shfl_xor(v.s[h].w, off, 64);
+            }
+            if (own_all) acc[h] = add4(acc[h], v.s[h]);      // (per float4, between the butterflies, as this kernel always had it: one region after them all compiles to other code)
+        }
+    }
+    __device__ __forceinline__ void take(const Value& v) {
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) acc[h] = add4(acc[h], v.s[h]);
+    }
+    __device__ __forceinline__ void park(int lane, const Value& v) const {
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) s_sum[lane * FEAT_NB + h] = v.s[h];
+    }
+    __device__ __forceinline__ Value parked(uint32_t i) const {
+        Value v;
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) v.s[h] = s_sum[i * FEAT_NB + h];
+        return v;
+    }
+};
+
+// feature_grad_reduce<2>'s body, written out, not on reduce_instance_runs: there it compiled to another schedule with one more s_waitcnt (523 instructions against 522).
+// The frame below is gsr_reduce.h's, line by line: change them together.
+template <int FEAT_NB>
+__device__ __forceinline__ void feature_grad_reduce_written_out(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets,
+                                                                const float4* __restrict__ slots, const uint32_t* __restrict__ flags,
+                                                                float* __restrict__ dL_dfeatures /*[P,C]*/, int C, int c0) {
     __shared__ float4 s_sum[64 * FEAT_NB];
     const int lane = threadIdx.x;
     const int64_t j = (int64_t)blockIdx.x * 64 + lane;
@@ -395,6 +455,28 @@ feature_grad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const 
     }
 }
 
+template <int FEAT_NB>
+__global__ void __launch_bounds__(64)
+feature_grad_reduce(int P, int64_t R, const uint32_t* __restrict__ order, const uint32_t* __restrict__ offsets, const float4* __restrict__ slots,
+                    const uint32_t* __restrict__ flags, float* __restrict__ dL_dfeatures /*[P,C]*/, int C, int c0) {
+    if constexpr (FEAT_NB == 2) {      // (see feature_grad_reduce_written_out)
+        feature_grad_reduce_written_out<2>(P, R, order, offsets, slots, flags, dL_dfeatures, C, c0);
+        return;
+    }
+    __shared__ float4 s_sum[64 * FEAT_NB];
+    FeatureGradOps<FEAT_NB> ops(slots, R, s_sum);
+    gsrw::reduce_instance_runs(P, order, offsets, flags, ops, [&](uint32_t g) {
+        float* row = dL_dfeatures + (int64_t)g * C + c0;
+#pragma unroll
+        for (int h = 0; h < FEAT_NB; ++h) {      // (wave-uniform tests)
+            if (c0 + 4 * h + 0 < C) row[4 * h + 0] = ops.acc[h].x;
+            if (c0 + 4 * h + 1 < C) row[4 * h + 1] = ops.acc[h].y;
+            if (c0 + 4 * h + 2 < C) row[4 * h + 2] = ops.acc[h].z;
+            if (c0 + 4 * h + 3 < C) row[4 * h + 3] = ops.acc[h].w;
+        }
+    });
+}
+
 }  // namespace
 
 // float4 per slot record of the group that starts with `remaining` channels to go: 16 channels per walk while more than 8 remain, then 8, then 4
@@ -404,15 +486,7 @@ static int feature_grad_nb(int remaining) {
 }
 
 GsrContribScratch gsr_carve_feature_grad(char* base, int64_t R, int C) {
-    GsrContribScratch w;
-    const size_t r = (size_t)(R > 0 ? R : 0);
-    size_t off = 0;
-    w.slots = reinterpret_cast<float4*>(base + off);
-    off += gsr_align128(r * 4 * (size_t)feature_grad_nb(C) * sizeof(float4));      // (the first group of a call is its widest)
-    w.flags = reinterpret_cast<uint32_t*>(base + off);
-    off += gsr_align128(r * sizeof(uint32_t));
-    w.bytes = off;
-    return w;
+    return gsr_carve_slots(base, R, feature_grad_nb(C));      // (the first group of a call is its widest)
 }
 
 void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out, hipStream_t st) {
@@ -427,9 +501,9 @@ void gsr_launch_render_features_defaults(const GsrCamDev& cam, int C, float* out
 }
 
 void gsr_launch_render_features(const GsrCamDev& cam, const GsrSavedFrame& f, const float* features, int C, float* out, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     if (n_band_tiles <= 0) return;
-    const int groups = (n_band_tiles + 7) / 8;
+    const int groups = gsr_tile_groups(n_band_tiles, 8);
     const bool vec4 = (C % 4 == 0) && (((uintptr_t)features) & 15) == 0;
     for (int c0 = 0; c0 < C; c0 += FEAT_G) {
         if (vec4)
@@ -443,9 +517,9 @@ void gsr_launch_render_features(const GsrCamDev& cam, const GsrSavedFrame& f, co
 
 void gsr_launch_render_features_backward(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* dL_dout, int C,
                                          const GsrContribScratch& w, float* dL_dfeatures, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     if (n_band_tiles <= 0 || P <= 0 || R <= 0) return;
-    const int groups = (n_band_tiles + 7) / 8;
+    const int groups = gsr_tile_groups(n_band_tiles, 8);
     for (int c0 = 0; c0 < C;) {      // one scratch region, reused group after group on the stream
         const int nb = feature_grad_nb(C - c0);
         (void)hipMemsetAsync(w.flags, 0, (size_t)R * 4, st);

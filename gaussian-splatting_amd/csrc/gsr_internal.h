@@ -173,6 +173,10 @@ static inline GsrBandRows gsr_band_rows(const GsrCamDev& cam) {
     return b;
 }
 
+// the band's tiles, and the launch groups that cover n of them (8 tiles per group: a wave per 8x8 block, 32 to a group; 16: a wave per half tile)
+static inline int gsr_band_tiles(const GsrCamDev& cam) { return cam.gx * (cam.tile_y1 - cam.tile_y0); }
+static inline int gsr_tile_groups(int n_tiles, int tiles_per_group) { return (n_tiles + tiles_per_group - 1) / tiles_per_group; }
+
 // ---- kernel launchers (one per translation unit) ----
 // preprocess.hip  (compiled with -ffp-contract=off)
 // (the key-producing launchers return their grid size: the number of entries of fs.wg_range they fill)
@@ -388,7 +392,8 @@ struct GsrContribScratch {
     uint32_t* flags;        // [R]     byte q != 0: slot q of the instance has a record
     size_t bytes;
 };
-GsrContribScratch gsr_carve_contrib(char* base, int64_t R);
+GsrContribScratch gsr_carve_slots(char* base, int64_t R, int nb /*float4 per slot record*/);      // contrib.hip; the one carve of this shape
+static inline GsrContribScratch gsr_carve_contrib(char* base, int64_t R) { return gsr_carve_slots(base, R, 1); }
 void gsr_launch_contribution_stats(const GsrCamDev& cam, int P, int64_t R, const GsrSavedFrame& f, const float* pixel_weight /*[H*W] or NULL*/,
                                    const GsrContribScratch& w, float* weight_sum, float* weight_max, int32_t* pixel_count /*each [P] or NULL*/,
                                    int accumulate, hipStream_t st);

@@ -19,6 +19,7 @@
 #include <cfloat>
 
 #include "gsr_internal.h"
+#include "gsr_reduce.h"
 
 namespace {
 
@@ -199,18 +200,6 @@ depth_normals_kernel(GsrNormalsFrame f, const float* __restrict__ depth, float* 
 }
 
 // ---- the fused loss -------------------------------------------------------------------------------------------------------------------------------
-// sum over the 256 threads in a fixed order (a tree over LDS); the total in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* s) {
-    const int tid = (int)threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) s[tid] += s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 __global__ void __launch_bounds__(256)
 normal_loss_kernel(GsrNormalsFrame f, const float* __restrict__ depth, const float* __restrict__ normals, const float* __restrict__ weight,
                    double* __restrict__ partials) {
@@ -235,17 +224,14 @@ normal_loss_kernel(GsrNormalsFrame f, const float* __restrict__ depth, const flo
         const float t = (q.ok && w != 0.f) ? w * (q.n[0] * n0 + q.n[1] * n1 + q.n[2] * n2) : 0.f;
         acc += 1.0 - (double)t;
     }
-    const double sum = block_sum_f64(acc, sSum);
+    const double sum = gsrw::block_sum_f64(acc, sSum);
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 __global__ void __launch_bounds__(256)
 normal_loss_sum_kernel(int n, double pixels, const double* __restrict__ partials, float* __restrict__ loss_out) {
     __shared__ double s[256];
-    double acc = 0.0;
-    for (int i = (int)threadIdx.x; i < n; i += 256) acc += partials[i];
-    const double sum = block_sum_f64(acc, s);
-    if (threadIdx.x == 0) loss_out[0] = (float)(sum / pixels);
+    gsrw::block_sum_partials_f64(n, partials, pixels, loss_out, s);
 }
 
 // dL/dnormals of the loss alone: -w Nd dL / (H W)

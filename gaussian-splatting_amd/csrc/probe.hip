@@ -143,8 +143,8 @@ void gsr_launch_pixel_probe_defaults(const GsrCamDev& cam, const GsrPixelProbeOu
 }
 
 void gsr_launch_pixel_probe(const GsrCamDev& cam, const GsrSavedFrame& f, const GsrPixelProbeOut& out, hipStream_t st) {
-    const int n_band_tiles = cam.gx * (cam.tile_y1 - cam.tile_y0);
+    const int n_band_tiles = gsr_band_tiles(cam);
     if (n_band_tiles <= 0) return;
-    const int groups = (n_band_tiles + 7) / 8;
+    const int groups = gsr_tile_groups(n_band_tiles, 8);
     hipLaunchKernelGGL(probe_walk, dim3(groups * 32), dim3(64), 0, st, cam, n_band_tiles, f.ranges, f.point_list, f.splats, f.n_contrib, out);
 }

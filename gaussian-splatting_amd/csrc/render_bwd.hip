@@ -722,6 +722,8 @@ bwd_plan_kernel(int tile0, int n_band_tiles, const uint4* __restrict__ block_ste
 // b * 2048 + k * 256 + t, k = 0..7 (coalesced), writes the three fp32 products of each and adds their exact fp64 values in k order; the 256
 // thread sums are added in LDS by a fixed tree.  bg_grad_finish adds the per-workgroup sums in a fixed order and rounds once to fp32.
 // No atomics, every output overwritten: two runs give the same bits.
+// (The tree is block_sum_f64 of gsr_reduce.h three values wide.  A shared N-value form compiled to other LDS accesses in both kernels -- the last
+// level read as two ds_read_b128 -- so it stays written out here.)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 bg_grad_kernel(int64_t npix, int W, int row0, int row1, const float* __restrict__ final_T /*NULL: T = 1*/, const float* __restrict__ dL_dpix,
