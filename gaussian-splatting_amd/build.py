@@ -17,6 +17,8 @@ Translation units and their flags:
                                         loss sum is fp64)
   mip.hip          -ffp-contract=off   (the per-Gaussian streaming kernels' flag: the sweep's dot products are explicit fmaf chains, the
                                         activations take correctly rounded divide / sqrt through intrinsics)
+  vq.hip           -ffp-contract=off   (the assignment's scores are the fmaf chains of v_mfma_f32_32x32x2_f32 and of explicit fmaf calls, the
+                                        same roundings in the host build through csrc/gsr_mfma.h; the update's sums are fp64)
   gsr_api.cpp                         (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
@@ -70,6 +72,7 @@ UNITS = [
     ("bilagrid.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("normals.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("mip.hip", ["-ffp-contract=off"]),
+    ("vq.hip", ["-ffp-contract=off"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

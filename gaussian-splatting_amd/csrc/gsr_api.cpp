@@ -1839,6 +1839,40 @@ int gsr_mip_activations_backward(int P, const float* raw_scales, const float* ra
     return GSR_OK;
 }
 
+// ---- vector quantisation: the two steps of a Lloyd iteration (vq.hip) ----
+static bool vq_sizes_ok(int P, int D, int K) { return P >= 0 && D >= 1 && D <= GSR_VQ_MAX_D && K >= 1 && K <= GSR_VQ_MAX_K; }
+
+size_t gsr_vq_scratch_bytes(int P, int D, int K) { return vq_sizes_ok(P, D, K) ? gsr_vq_scratch_bytes_impl(P, D, K) : 0; }
+
+int gsr_vq_assign(int P, int D, int K, const float* rows, const float* codebook, int32_t* idx, float* dist2, void* scratch, void* stream) {
+    if (!vq_sizes_ok(P, D, K))
+        return fail(GSR_ERR_INVALID_ARG, "vq: need 0 <= P, 1 <= D <= 64, 1 <= K <= 65536, got P = " + std::to_string(P) + ", D = " + std::to_string(D) +
+                                             ", K = " + std::to_string(K));
+    if (P == 0) return GSR_OK;
+    if (!rows || !codebook || !idx || !dist2 || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)scratch & 15) return fail(GSR_ERR_INVALID_ARG, "vq: scratch must be 16-byte aligned");
+    gsr_launch_vq_assign(P, D, K, rows, codebook, idx, dist2, scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_vq_update(int P, int D, int K, const float* rows, const float* weights, const int32_t* idx, float* codebook, float* mass, void* scratch,
+                  void* stream) {
+    if (!vq_sizes_ok(P, D, K))
+        return fail(GSR_ERR_INVALID_ARG, "vq: need 0 <= P, 1 <= D <= 64, 1 <= K <= 65536, got P = " + std::to_string(P) + ", D = " + std::to_string(D) +
+                                             ", K = " + std::to_string(K));
+    if (!codebook || !mass) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if (P == 0) {      // every cluster is empty: the centroids stay, the masses are zero
+        HIP_OK(hipMemsetAsync(mass, 0, (size_t)K * sizeof(float), (hipStream_t)stream));
+        return GSR_OK;
+    }
+    if (!rows || !idx || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only weights may be NULL)");
+    if ((uintptr_t)scratch & 15) return fail(GSR_ERR_INVALID_ARG, "vq: scratch must be 16-byte aligned");
+    gsr_launch_vq_update(P, D, K, rows, weights, idx, codebook, mass, scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

@@ -506,6 +506,14 @@ void gsr_launch_mip_activations(int P, const float* raw_scales, const float* raw
                                 float* opacity_out, hipStream_t st);
 void gsr_launch_mip_activations_backward(int P, const float* raw_scales, const float* raw_opacity, const float* filter, const float* dL_dscales,
                                          const float* dL_dopacity, float* dL_draw_scales, float* dL_draw_opacity, hipStream_t st);
+// vq.hip: vector quantisation.  One scratch layout serves both steps: the assignment's centroid norms and LDS images, the
+// update's sort buffers, segment tables and per-chunk fp64 partial sums.  weights may be NULL (1).
+#define GSR_VQ_MAX_D 64
+#define GSR_VQ_MAX_K 65536
+size_t gsr_vq_scratch_bytes_impl(int P, int D, int K);
+void gsr_launch_vq_assign(int P, int D, int K, const float* rows, const float* codebook, int32_t* idx, float* dist2, void* scratch, hipStream_t st);
+void gsr_launch_vq_update(int P, int D, int K, const float* rows, const float* weights, const int32_t* idx, float* codebook, float* mass,
+                          void* scratch, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

@@ -173,6 +173,9 @@ SIGNATURES = {
     "gsr_mip_filter_3d": (C.c_int, [C.c_int, _vp, C.c_int] + [_vp] * 5),
     "gsr_mip_activations": (C.c_int, [C.c_int] + [_vp] * 6),
     "gsr_mip_activations_backward": (C.c_int, [C.c_int] + [_vp] * 8),
+    "gsr_vq_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
+    "gsr_vq_assign": (C.c_int, [C.c_int] * 3 + [_vp] * 6),
+    "gsr_vq_update": (C.c_int, [C.c_int] * 3 + [_vp] * 7),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

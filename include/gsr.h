@@ -789,6 +789,33 @@ int gsr_mip_activations_backward(int P, const float* raw_scales, const float* ra
                                  float* dL_draw_opacity, void* stream);
 
 /*
+ * Vector quantisation of per-Gaussian parameters: the two steps of a Lloyd (k-means) iteration over rows [P,D] and a codebook [K,D], what
+ * "Compressed 3D Gaussian Splatting" (Niedermayr et al., CVPR 2024), Compact3D, LightGaussian and gsplat's PngCompression run over the SH
+ * coefficients, scales and rotations of a trained scene.  gsr_scene/compress.py is the package side.  (Additive, the ABI version stays 4.)
+ * Limits: 0 <= P, 1 <= D <= 64, 1 <= K <= 65536; anything else is GSR_ERR_INVALID_ARG (gsr_vq_scratch_bytes: 0).  scratch:
+ * gsr_vq_scratch_bytes(P, D, K) bytes, 16-byte aligned, caller-owned, shared by both calls; its contents need not be initialised.
+ *
+ * gsr_vq_assign: idx[p] = argmin_k |x_p - c_k|^2, evaluated as argmin_k (|c_k|^2 - 2 x_p . c_k) in fp32 on the matrix pipe, never writing a
+ * P x K block.  NUMERICS CONTRACT.  The score of (p, k) is the chain s = |c_k|^2; s = fmaf(-2 x_pi, c_ki, s) for ascending i, with
+ * |c_k|^2 = fmaf(c_ki, c_ki, .) ascending from 0: the chosen centroid is within (D + 4) 2^-23 (|x|^2 + |c_got|^2 + |c_best|^2) of the best
+ * squared distance.  The form cancels when |x| is large against the distances: centre the rows first (the argmin is translation-invariant;
+ * gsr_scene.compress.kmeans does).  An exact fp32 tie of scores goes to the LOWEST index.  dist2[p] is recomputed for the winner directly,
+ * d = 0; d = fmaf(x_i - c_i, x_i - c_i, d) ascending -- not from the score.  Containment: a row with a NaN / inf component
+ * gets idx -1 and dist2 0 and changes no other row; a centroid with a NaN / inf component (or whose norm overflows) never wins; when no
+ * centroid is finite (or every score of a row overflows) idx is -1.  P == 0 succeeds without a launch.
+ *
+ * gsr_vq_update: codebook[k] = (float)(sum w_p x_p / sum w_p) and mass[k] = (float) sum w_p over the rows with idx[p] == k, the sums in fp64 in
+ * a fixed order (stable sort by idx, rows of a cluster in ascending p, segments cut into chunks of 256 rows that are added in chunk order): no
+ * floating-point atomics, two runs give the same bits.  idx outside [0, K) (-1 of the assignment) belongs to nobody.  A cluster whose weights
+ * sum to zero KEEPS its centroid, bit for bit, and reports mass 0.  weights NULL: 1; a negative, NaN or inf weight counts as 0, and a row of
+ * weight 0 adds nothing whatever it holds.  P == 0: every mass is 0.
+ */
+size_t gsr_vq_scratch_bytes(int P, int D, int K);                            /* 0: unsupported sizes */
+int gsr_vq_assign(int P, int D, int K, const float* rows, const float* codebook, int32_t* idx, float* dist2, void* scratch, void* stream);
+int gsr_vq_update(int P, int D, int K, const float* rows, const float* weights_or_null, const int32_t* idx,
+                  float* codebook /* in: kept where a cluster is empty; out */, float* mass /* [K] */, void* scratch, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points

@@ -83,6 +83,40 @@ def audit(path: str, flags, extra):
     return rows
 
 
+def resources(path: str, flags, extra=()):
+    """{kernel (demangle_short): {"vgprs", "agprs", "sgprs", "lds_bytes", "scratch_bytes", "vgpr_spill_count", "sgpr_spill_count"}} from the code-object
+    metadata of one translation unit.  scratch_bytes > 0 with no spill counted is a private array the compiler kept in memory."""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only",
+               "-o", out, path] + list(flags) + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(r.stderr[-2000:])
+        s = open(out).read()
+    rows = {}
+    for entry in re.split(r"^  - (?=\.)", s[s.index("amdhsa.kernels:"):], flags=re.M)[1:]:
+        f = dict(re.findall(r"^\s*\.(\w+):\s*(\S+)\s*$", entry, re.M))
+        rows[demangle_short(f["name"])] = {
+            "vgprs": int(f["vgpr_count"]), "agprs": int(f.get("agpr_count", 0)), "sgprs": int(f["sgpr_count"]), "lds_bytes": int(f["group_segment_fixed_size"]),
+            "scratch_bytes": int(f["private_segment_fixed_size"]), "vgpr_spill_count": int(f["vgpr_spill_count"]), "sgpr_spill_count": int(f["sgpr_spill_count"])}
+    return rows
+
+
+def instruction_counts(path: str, flags, mnemonic: str, extra=()):
+    """{kernel (demangle_short): how often `mnemonic` (e.g. v_mfma_f32_32x32x2_f32) occurs in its gfx950 code} for every kernel of one translation unit."""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only",
+               "-o", out, path] + list(flags) + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(r.stderr[-2000:])
+        s = open(out).read()
+    return {demangle_short(m.group(1)): len(re.findall(r"^\s+" + re.escape(mnemonic) + r"\s", m.group(2), re.M))
+            for m in re.finditer(r"^(_Z\w+): ; @.*?\n(.*?)^\.Lfunc_end", s, re.S | re.M)}
+
+
 def forward_walk_step(extra=()):
     """Instruction mix of ONE step of the forward blend's survivor walk in the inference build (render_fwd_wave_bf<true, 1, false>): the first unrolled
     copy of the inner loop's body, from the loop header to its closing branch -> {"valu": n, "salu": n, "ds": n}.  The kernel is bound by issue slots
