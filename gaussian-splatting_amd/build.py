@@ -19,6 +19,9 @@ Translation units and their flags:
                                         activations take correctly rounded divide / sqrt through intrinsics)
   vq.hip           -ffp-contract=off   (the assignment's scores are the fmaf chains of v_mfma_f32_32x32x2_f32 and of explicit fmaf calls, the
                                         same roundings in the host build through csrc/gsr_mfma.h; the update's sums are fp64)
+  tsdf.hip         -ffp-contract=off   (every operation of the integrate that decides something -- pixel, validity, truncation -- is one correctly
+                                        rounded fp32 operation through an intrinsic or an explicit fmaf: the host build takes the same decisions;
+                                        the extraction is integers plus one interpolation per vertex)
   gsr_api.cpp                         (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
@@ -73,6 +76,7 @@ UNITS = [
     ("normals.hip", ["-ffp-contract=fast", "-fno-slp-vectorize"]),
     ("mip.hip", ["-ffp-contract=off"]),
     ("vq.hip", ["-ffp-contract=off"]),
+    ("tsdf.hip", ["-ffp-contract=off"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

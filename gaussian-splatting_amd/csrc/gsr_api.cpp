@@ -1873,6 +1873,81 @@ int gsr_vq_update(int P, int D, int K, const float* rows, const float* weights, 
     return GSR_OK;
 }
 
+// ---- TSDF fusion and marching tetrahedra (tsdf.hip) ----
+static int tsdf_dims_checked(int nx, int ny, int nz, int64_t* cells) {
+    if (nx < 0 || ny < 0 || nz < 0)
+        return fail(GSR_ERR_INVALID_ARG, "tsdf: the volume's dimensions must be >= 0, got " + std::to_string(nx) + " x " + std::to_string(ny) + " x " +
+                                             std::to_string(nz));
+    const bool empty = nx == 0 || ny == 0 || nz == 0;
+    if (!empty && ((int64_t)nx * ny >= ((int64_t)1 << 31) || (int64_t)nx * ny * nz >= ((int64_t)1 << 31)))
+        return fail(GSR_ERR_INVALID_ARG, "tsdf: a volume of " + std::to_string(nx) + " x " + std::to_string(ny) + " x " + std::to_string(nz) +
+                                             " voxels has 2^31 or more");
+    *cells = empty ? 0 : (int64_t)nx * ny * nz;
+    return GSR_OK;
+}
+
+int gsr_tsdf_integrate(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float sdf_trunc, float near_z, int V,
+                       const float* cameras, int H, int W, const float* depth, const float* color, float* tsdf, float* weight, float* rgb,
+                       void* stream) {
+    int64_t cells = 0;
+    if (int rc = tsdf_dims_checked(nx, ny, nz, &cells)) return rc;
+    if (V < 0) return fail(GSR_ERR_INVALID_ARG, "tsdf: V < 0");
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31))
+        return fail(GSR_ERR_INVALID_ARG, "tsdf: the depth maps must be at least 1 x 1 and below 2^31 pixels, got H = " + std::to_string(H) + ", W = " +
+                                             std::to_string(W));
+    if (!(voxel_size > 0.f) || !(sdf_trunc > 0.f) || !(near_z >= 0.f) || !std::isfinite(voxel_size) || !std::isfinite(sdf_trunc) ||
+        !std::isfinite(near_z) || !std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(oz))
+        return fail(GSR_ERR_INVALID_ARG, "tsdf: need voxel_size > 0, sdf_trunc > 0, near >= 0 and a finite origin");
+    if (V == 0 || cells == 0) return GSR_OK;
+    if (!cameras || !depth || !tsdf || !weight) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only color and rgb may be NULL)");
+    if ((color == nullptr) != (rgb == nullptr)) return fail(GSR_ERR_INVALID_ARG, "tsdf: give color and rgb together or neither");
+    gsr_launch_tsdf_integrate(nx, ny, nz, ox, oy, oz, voxel_size, sdf_trunc, near_z, V, cameras, H, W, depth, color, tsdf, weight, rgb,
+                              (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+static bool mesh_sizes_ok(int nx, int ny, int nz) {
+    return nx >= 0 && ny >= 0 && nz >= 0 && (nx == 0 || ny == 0 || nz == 0 || ((int64_t)nx * ny <= GSR_MESH_MAX_VOXELS &&
+                                                                             (int64_t)nx * ny * nz <= GSR_MESH_MAX_VOXELS));
+}
+static bool mesh_has_cell(int nx, int ny, int nz) { return nx >= 2 && ny >= 2 && nz >= 2; }
+
+size_t gsr_mesh_scratch_bytes(int nx, int ny, int nz) { return mesh_sizes_ok(nx, ny, nz) ? gsr_mesh_scratch_bytes_impl(nx, ny, nz) : 0; }
+
+int gsr_mesh_count(int nx, int ny, int nz, const float* tsdf, const float* weight, float min_weight, void* scratch, int32_t* counts_out,
+                   void* stream) {
+    if (!mesh_sizes_ok(nx, ny, nz))
+        return fail(GSR_ERR_INVALID_ARG, "mesh: need 0 <= nx, ny, nz and nx ny nz <= " + std::to_string(GSR_MESH_MAX_VOXELS) + ", got " +
+                                             std::to_string(nx) + " x " + std::to_string(ny) + " x " + std::to_string(nz));
+    if (std::isnan(min_weight)) return fail(GSR_ERR_INVALID_ARG, "mesh: min_weight is NaN");
+    if (!counts_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if (!mesh_has_cell(nx, ny, nz)) {      // no cell: an empty mesh, no launch
+        HIP_OK(hipMemsetAsync(counts_out, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
+        return GSR_OK;
+    }
+    if (!tsdf || !weight || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "mesh: scratch must be 128-byte aligned");
+    gsr_launch_mesh_count(nx, ny, nz, tsdf, weight, min_weight, scratch, counts_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, const float* tsdf, const float* rgb, void* scratch,
+                  int nv, int nf, float* vertices, float* colors, int32_t* faces, void* stream) {
+    if (!mesh_sizes_ok(nx, ny, nz))
+        return fail(GSR_ERR_INVALID_ARG, "mesh: need 0 <= nx, ny, nz and nx ny nz <= " + std::to_string(GSR_MESH_MAX_VOXELS) + ", got " +
+                                             std::to_string(nx) + " x " + std::to_string(ny) + " x " + std::to_string(nz));
+    if (nv < 0 || nf < 0) return fail(GSR_ERR_INVALID_ARG, "mesh: nv < 0 or nf < 0");
+    if (nv == 0 || !mesh_has_cell(nx, ny, nz)) return GSR_OK;
+    if (!tsdf || !scratch || !vertices || (nf > 0 && !faces)) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only rgb and colors may be NULL)");
+    if ((rgb == nullptr) != (colors == nullptr)) return fail(GSR_ERR_INVALID_ARG, "mesh: give rgb and colors together or neither");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "mesh: scratch must be 128-byte aligned");
+    gsr_launch_mesh_emit(nx, ny, nz, ox, oy, oz, voxel_size, tsdf, rgb, scratch, nv, nf, vertices, colors, faces, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

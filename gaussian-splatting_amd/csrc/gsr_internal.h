@@ -514,6 +514,17 @@ size_t gsr_vq_scratch_bytes_impl(int P, int D, int K);
 void gsr_launch_vq_assign(int P, int D, int K, const float* rows, const float* codebook, int32_t* idx, float* dist2, void* scratch, hipStream_t st);
 void gsr_launch_vq_update(int P, int D, int K, const float* rows, const float* weights, const int32_t* idx, float* codebook, float* mass,
                           void* scratch, hipStream_t st);
+// tsdf.hip: TSDF fusion and marching tetrahedra.  The integrate is one kernel over all views; the extraction leaves per-voxel
+// class, vertex mask and in-workgroup prefixes in the scratch at the count and reads them back at the emit (rs_scan of sort.hip in between).
+#define GSR_MESH_MAX_VOXELS 178956970      // 12 faces per cell stay below 2^31
+size_t gsr_mesh_scratch_bytes_impl(int nx, int ny, int nz);
+void gsr_launch_tsdf_integrate(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float sdf_trunc, float near_z, int V,
+                               const float* cameras /*[V,16]*/, int H, int W, const float* depth, const float* color /*or NULL*/, float* tsdf,
+                               float* weight, float* rgb /*or NULL*/, hipStream_t st);
+void gsr_launch_mesh_count(int nx, int ny, int nz, const float* tsdf, const float* weight, float min_weight, void* scratch, int32_t* counts_out,
+                           hipStream_t st);
+void gsr_launch_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, const float* tsdf, const float* rgb /*or NULL*/,
+                          void* scratch, int nv, int nf, float* vertices, float* colors /*or NULL*/, int32_t* faces, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

@@ -176,6 +176,10 @@ SIGNATURES = {
     "gsr_vq_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
     "gsr_vq_assign": (C.c_int, [C.c_int] * 3 + [_vp] * 6),
     "gsr_vq_update": (C.c_int, [C.c_int] * 3 + [_vp] * 7),
+    "gsr_tsdf_integrate": (C.c_int, [C.c_int] * 3 + [C.c_float] * 6 + [C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 6),
+    "gsr_mesh_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
+    "gsr_mesh_count": (C.c_int, [C.c_int] * 3 + [_vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "gsr_mesh_emit": (C.c_int, [C.c_int] * 3 + [C.c_float] * 4 + [_vp] * 3 + [C.c_int] * 2 + [_vp] * 4),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

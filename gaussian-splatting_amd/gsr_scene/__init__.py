@@ -23,6 +23,7 @@ __all__ = ["gaussian_attribute_names", "save_gaussians_ply", "load_gaussians_ply
 # 3DGS-MCMC density control (cap, relocation, noise): gsr_scene.mcmc
 # 3D smoothing filter of Mip-Splatting (camera sweep, filtered activations): gsr_scene.mip
 # vector-quantised compression (k-means codebooks, 16-bit indices, .npz): gsr_scene.compress
+# TSDF fusion of rendered depth and marching-tetrahedra mesh extraction (TSDFVolume, mesh .ply): gsr_scene.mesh
 
 
 def gaussian_attribute_names(n_rest: int, n_scale: int = 3, n_rot: int = 4):

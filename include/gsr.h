@@ -816,6 +816,58 @@ int gsr_vq_update(int P, int D, int K, const float* rows, const float* weights_o
                   float* codebook /* in: kept where a cluster is empty; out */, float* mass /* [K] */, void* scratch, void* stream);
 
 /*
+ * TSDF fusion of rendered depth maps and mesh extraction: the step 2DGS, Gaussian Opacity Fields, RaDe-GS and PGSR end with.
+ * gsr_scene/mesh.py is the package side.  (Additive, the ABI version stays 4.)
+ *
+ * The volume is dense, nx x ny x nz voxels stored [nz,ny,nx] (x fastest); voxel (ix,iy,iz) sits at origin + voxel_size (ix,iy,iz).  State:
+ * tsdf (fp32, the running weighted mean, in [-1,1]), weight (fp32, a count of observations) and optionally rgb [3,nz,ny,nx].  A fresh volume
+ * is tsdf = 1, weight = 0, rgb = 0.  nx ny nz >= 2^31 is refused.
+ *
+ * gsr_tsdf_integrate folds V views into the volume in ONE kernel (the volume is read and written at most once per call).  A camera record
+ * is the 16 floats of gsr_mip_filter_3d; the principal point is (W / 2, H / 2) of the call's W and H (the package checks that every record
+ * carries the same two numbers).  depth [V,H,W] is view-space z; color [V,3,H,W] goes with rgb (both or neither is used).  For a voxel at
+ * xyz and view v, in view order, with cam = xyz R + T and z = cam.z:
+ *   skip unless z > near;   px = floor(focal_x cam.x / z + W / 2), py = floor(focal_y cam.y / z + H / 2)  (the nearest pixel centre under the
+ *   rasterizer's pixel convention);   skip unless 0 <= px < W and 0 <= py < H;   d = depth[v,py,px];   skip unless d is finite and d > 0;
+ *   sdf = d - z;   skip when sdf < -sdf_trunc;   otherwise s += min(1, sdf / sdf_trunc), n += 1, c += color[v,:,py,px].
+ * After all views, when n > 0:  tsdf' = (tsdf weight + s) / (weight + n), rgb likewise, weight' = weight + n.  A voxel with n == 0 is not
+ * written.  This is Curless-Levoy's (and Open3D's) update with weight 1 per observation, folded over the call's views.
+ * NUMERICS CONTRACT.  cam is three fmaf chains, fmaf(x, R0j, fmaf(y, R1j, fmaf(z, R2j, Tj))); every product, quotient, sum and comparison
+ * named above is one correctly rounded fp32 operation, the sums run in view order, and there are no atomics: two runs give the same bits.
+ * Non-finite input: a NaN / inf depth pixel is an invalid pixel; a record with a non-finite entry contributes to no
+ * voxel; nothing spreads.  Limits: nx, ny, nz >= 0, V >= 0, H, W >= 1 (H W < 2^31), voxel_size > 0, sdf_trunc > 0, near >= 0, all finite;
+ * anything else is GSR_ERR_INVALID_ARG.  V == 0 or an empty volume succeeds without a launch.
+ *
+ * The mesh is INDEXED and comes from marching tetrahedra: each cell (ix..ix+1, iy..iy+1, iz..iz+1) is cut into the six Kuhn tetrahedra, for
+ * the axis permutation pi (in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx) the corners v0 = (0,0,0), v1 = v0 + e_pi(1),
+ * v2 = v1 + e_pi(2), v3 = (1,1,1).  Every tetrahedron edge runs from a grid point in one of seven directions, numbered (1,0,0), (0,1,0),
+ * (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1), and is owned by its lower grid point: a mesh vertex IS (owner voxel, direction).
+ *   A voxel is observed when weight >= min_weight and its tsdf is finite; a cell is valid when its eight corners are observed; only valid
+ *   cells emit faces.  A corner is inside when tsdf < 0, outside otherwise.  A vertex exists on an edge iff its ends differ in that and at
+ *   least one valid cell contains the edge; it sits at p0 + s0 / (s0 - s1) (p1 - p0), its colour interpolated with the same ratio.  A
+ *   tetrahedron emits 1 face for 1 or 3 inside corners, 2 for 2.  The winding comes from the case and the tetrahedron's orientation, never
+ *   from the computed geometry: face normals point to the outside (positive tsdf), zero-area faces included, which are kept.
+ *   With e_pq the vertex on the edge of tetrahedron corners p and q: one inside corner a (or one outside corner a) and the others b < c < d
+ *   give the face (e_ab, e_ac, e_ad) or (e_ab, e_ad, e_ac); inside corners a < b and outside corners c < d give the quad (e_ac, e_ad, e_bd, e_bc)
+ *   or (e_ac, e_bc, e_bd, e_ad), emitted as (q0, q1, q2), (q0, q2, q3) -- in each case the winding that faces outside.
+ *   Order: vertices by (owner voxel index, direction), faces by (cell index, tetrahedron, face).
+ * gsr_mesh_count classifies, counts and scans (fixed order, integers only) and leaves {vertices, faces} in counts_out (int32 [2], device);
+ * the caller reads the two numbers -- the one synchronisation -- allocates, and gsr_mesh_emit writes vertices [nv,3], colors [nv,3]
+ * (with rgb; both or neither) and faces [nf,3] from the SAME scratch, volume and min_weight's classification.  Nothing is written past nv
+ * vertices or nf faces.  nv == 0 succeeds without a launch, as does a volume without a cell.  scratch: gsr_mesh_scratch_bytes bytes,
+ * 128-byte aligned, caller-owned; its contents need not be initialised.  Extraction is limited to nx ny nz <= 178956970 (12 faces per
+ * cell fit int32); gsr_mesh_scratch_bytes returns 0 beyond.
+ */
+int gsr_tsdf_integrate(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float sdf_trunc, float near_z, int V,
+                       const float* cameras, int H, int W, const float* depth, const float* color_or_null, float* tsdf, float* weight,
+                       float* rgb_or_null, void* stream);
+size_t gsr_mesh_scratch_bytes(int nx, int ny, int nz);                       /* 0: unsupported sizes */
+int gsr_mesh_count(int nx, int ny, int nz, const float* tsdf, const float* weight, float min_weight, void* scratch, int32_t* counts_out,
+                   void* stream);
+int gsr_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, const float* tsdf, const float* rgb_or_null,
+                  void* scratch, int nv, int nf, float* vertices, float* colors_or_null, int32_t* faces, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points
