@@ -22,6 +22,9 @@ Translation units and their flags:
   tsdf.hip         -ffp-contract=off   (every operation of the integrate that decides something -- pixel, validity, truncation -- is one correctly
                                         rounded fp32 operation through an intrinsic or an explicit fmaf: the host build takes the same decisions;
                                         the extraction is integers plus one interpolation per vertex)
+  meshops.hip      -ffp-contract=off   (labels, counts and compaction are integers; the normals' and the smoothing's sums are fp64 operations
+                                        written one by one in ascending face order: without contraction the host build and the numpy reference
+                                        perform the same ones)
   gsr_api.cpp                         (host glue, C ABI)
 UNITS below is the one table of these flags: tools/isa_audit.py and tests/simt_build.py load it from this file.
 The library is built IN-TREE (gaussian-splatting_amd/lib/) so it travels to the GPU box with the snapshot.
@@ -77,6 +80,7 @@ UNITS = [
     ("mip.hip", ["-ffp-contract=off"]),
     ("vq.hip", ["-ffp-contract=off"]),
     ("tsdf.hip", ["-ffp-contract=off"]),
+    ("meshops.hip", ["-ffp-contract=off"]),
     ("gsr_api.cpp", ["-x", "hip"]),
 ]
 

@@ -1948,6 +1948,94 @@ int gsr_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float vo
     return GSR_OK;
 }
 
+// ---- mesh clean-up: components, compaction, normals, smoothing (meshops.hip) ----
+static bool meshops_sizes_ok(int nv, int nf) { return nv >= 0 && nf >= 0 && 3 * (int64_t)nf < ((int64_t)1 << 31); }
+static int meshops_sizes_checked(int nv, int nf) {
+    if (!meshops_sizes_ok(nv, nf))
+        return fail(GSR_ERR_INVALID_ARG, "meshops: need 0 <= nv and 0 <= 3 nf < 2^31, got nv = " + std::to_string(nv) + ", nf = " + std::to_string(nf));
+    return GSR_OK;
+}
+static int g_mesh_component_rounds = 0;
+
+size_t gsr_meshops_scratch_bytes(int nv, int nf) { return meshops_sizes_ok(nv, nf) ? gsr_meshops_scratch_bytes_impl(nv, nf) : 0; }
+
+int gsr_mesh_components(int nv, int nf, const int32_t* faces, int32_t* vertex_label, int32_t* face_count, void* scratch, void* stream) {
+    if (int rc = meshops_sizes_checked(nv, nf)) return rc;
+    g_mesh_component_rounds = 0;
+    if (nv == 0) {      // nothing to label: the call still synchronises
+        HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+        return GSR_OK;
+    }
+    if ((nf > 0 && !faces) || !vertex_label || !face_count || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "meshops: scratch must be 128-byte aligned");
+    const int rc = gsr_launch_mesh_components(nv, nf, faces, vertex_label, face_count, scratch, (hipStream_t)stream, &g_mesh_component_rounds);
+    HIP_OK(hipGetLastError());
+    if (rc < 0) return fail(GSR_ERR_HIP, "meshops: reading the round word back failed");
+    if (rc > 0)
+        return fail(GSR_ERR_UNSUPPORTED, "meshops: the components did not settle within " + std::to_string(gsr_meshops_round_cap(nv)) + " rounds (nv = " +
+                                          std::to_string(nv) + ", nf = " + std::to_string(nf) + ")");
+    return GSR_OK;
+}
+
+int gsr_mesh_components_rounds(void) { return g_mesh_component_rounds; }
+
+int gsr_mesh_compact_count(int nv, int nf, const int32_t* faces, const uint8_t* keep_face, void* scratch, int32_t* counts_out, void* stream) {
+    if (int rc = meshops_sizes_checked(nv, nf)) return rc;
+    if (!counts_out) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if (nv == 0 || nf == 0) {      // no row can be a face: an empty mesh, no launch
+        HIP_OK(hipMemsetAsync(counts_out, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
+        return GSR_OK;
+    }
+    if (!faces || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only keep_face may be NULL)");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "meshops: scratch must be 128-byte aligned");
+    gsr_launch_mesh_compact_count(nv, nf, faces, keep_face, scratch, counts_out, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mesh_compact_emit(int nv, int nf, const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep_face, void* scratch,
+                          int nv_out, int nf_out, float* vertices_out, float* colors_out, int32_t* faces_out, void* stream) {
+    if (int rc = meshops_sizes_checked(nv, nf)) return rc;
+    if (nv_out < 0 || nf_out < 0) return fail(GSR_ERR_INVALID_ARG, "meshops: nv_out < 0 or nf_out < 0");
+    if (nv_out == 0 || nv == 0 || nf == 0) return GSR_OK;      // (a kept face keeps three vertices: no vertex, no face)
+    if (!vertices || !faces || !scratch || !vertices_out || (nf_out > 0 && !faces_out))
+        return fail(GSR_ERR_INVALID_ARG, "NULL pointer (only colors, colors_out and keep_face may be NULL)");
+    if ((colors == nullptr) != (colors_out == nullptr)) return fail(GSR_ERR_INVALID_ARG, "meshops: give colors and colors_out together or neither");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "meshops: scratch must be 128-byte aligned");
+    gsr_launch_mesh_compact_emit(nv, nf, vertices, colors, faces, keep_face, scratch, nv_out, nf_out, vertices_out, colors_out, faces_out,
+                                 (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mesh_vertex_normals(int nv, int nf, const float* vertices, const int32_t* faces, float* normals_out, void* scratch, void* stream) {
+    if (int rc = meshops_sizes_checked(nv, nf)) return rc;
+    if (nv == 0) return GSR_OK;
+    if (!vertices || (nf > 0 && !faces) || !normals_out || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "meshops: scratch must be 128-byte aligned");
+    gsr_launch_mesh_vertex_normals(nv, nf, vertices, faces, normals_out, scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mesh_smooth(int nv, int nf, const float* vertices, const int32_t* faces, int iterations, float lambda, float mu, float* vertices_out,
+                    void* scratch, void* stream) {
+    if (int rc = meshops_sizes_checked(nv, nf)) return rc;
+    if (iterations < 0 || iterations > (1 << 20)) return fail(GSR_ERR_INVALID_ARG, "meshops: need 0 <= iterations <= 2^20, got " + std::to_string(iterations));
+    if (std::isnan(lambda) || std::isnan(mu)) return fail(GSR_ERR_INVALID_ARG, "meshops: lambda or mu is NaN");
+    if (nv == 0) return GSR_OK;
+    if (!vertices || (nf > 0 && !faces) || !vertices_out || !scratch) return fail(GSR_ERR_INVALID_ARG, "NULL pointer");
+    if (vertices == vertices_out) return fail(GSR_ERR_INVALID_ARG, "meshops: vertices_out must not be the input (the input is never written)");
+    if ((uintptr_t)scratch & 127) return fail(GSR_ERR_INVALID_ARG, "meshops: scratch must be 128-byte aligned");
+    if (iterations == 0) {
+        HIP_OK(hipMemcpyAsync(vertices_out, vertices, (size_t)nv * 3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return GSR_OK;
+    }
+    gsr_launch_mesh_smooth(nv, nf, vertices, faces, iterations, lambda, mu, vertices_out, scratch, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return GSR_OK;
+}
+
 size_t gsr_knn_scratch_bytes(int N) { return gsr_knn_scratch_bytes_impl(N); }
 
 int gsr_knn_mean_dist2(int N, const float* points, float* mean_dist2, void* scratch, void* stream) {

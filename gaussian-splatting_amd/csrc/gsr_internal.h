@@ -525,6 +525,20 @@ void gsr_launch_mesh_count(int nx, int ny, int nz, const float* tsdf, const floa
                            hipStream_t st);
 void gsr_launch_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, const float* tsdf, const float* rgb /*or NULL*/,
                           void* scratch, int nv, int nf, float* vertices, float* colors /*or NULL*/, int32_t* faces, hipStream_t st);
+// meshops.hip: clean-up of an indexed mesh.  One scratch layout serves the five operations.  The components launcher runs its rounds
+// of hook + compress, reads one device word per round and synchronises the stream: 0 = done, 1 = the round cap was reached, -1 = a HIP call failed.
+size_t gsr_meshops_scratch_bytes_impl(int nv, int nf);
+int gsr_meshops_round_cap(int nv);      // 2 ceil(log2(nv + 1)) + 8
+int gsr_launch_mesh_components(int nv, int nf, const int32_t* faces, int32_t* vertex_label, int32_t* face_count, void* scratch, hipStream_t st,
+                               int* rounds_out);
+void gsr_launch_mesh_compact_count(int nv, int nf, const int32_t* faces, const uint8_t* keep /*or NULL*/, void* scratch, int32_t* counts_out,
+                                   hipStream_t st);
+void gsr_launch_mesh_compact_emit(int nv, int nf, const float* vertices, const float* colors /*or NULL*/, const int32_t* faces,
+                                  const uint8_t* keep /*or NULL*/, void* scratch, int nv_out, int nf_out, float* vertices_out,
+                                  float* colors_out /*or NULL*/, int32_t* faces_out, hipStream_t st);
+void gsr_launch_mesh_vertex_normals(int nv, int nf, const float* vertices, const int32_t* faces, float* normals, void* scratch, hipStream_t st);
+void gsr_launch_mesh_smooth(int nv, int nf, const float* vertices, const int32_t* faces, int iterations, float lambda, float mu,
+                            float* vertices_out, void* scratch, hipStream_t st);
 // knn.hip
 size_t gsr_knn_scratch_bytes_impl(int N);
 void gsr_launch_knn(int N, const float* points, float* out, void* scratch, hipStream_t st);

@@ -180,6 +180,13 @@ SIGNATURES = {
     "gsr_mesh_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
     "gsr_mesh_count": (C.c_int, [C.c_int] * 3 + [_vp, _vp, C.c_float, _vp, _vp, _vp]),
     "gsr_mesh_emit": (C.c_int, [C.c_int] * 3 + [C.c_float] * 4 + [_vp] * 3 + [C.c_int] * 2 + [_vp] * 4),
+    "gsr_meshops_scratch_bytes": (C.c_size_t, [C.c_int] * 2),
+    "gsr_mesh_components": (C.c_int, [C.c_int] * 2 + [_vp] * 5),
+    "gsr_mesh_components_rounds": (C.c_int, []),
+    "gsr_mesh_compact_count": (C.c_int, [C.c_int] * 2 + [_vp] * 5),
+    "gsr_mesh_compact_emit": (C.c_int, [C.c_int] * 2 + [_vp] * 5 + [C.c_int] * 2 + [_vp] * 4),
+    "gsr_mesh_vertex_normals": (C.c_int, [C.c_int] * 2 + [_vp] * 5),
+    "gsr_mesh_smooth": (C.c_int, [C.c_int] * 2 + [_vp, _vp, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp]),
     "gsr_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "gsr_ssim_forward": (C.c_int, [C.c_int] * 3 + [_vp] * 7),

@@ -7,6 +7,11 @@ distance volume; marching tetrahedra turns the volume into an indexed triangle m
         .extract(min_weight=1.0) -> Mesh(vertices, faces, colors)          marching tetrahedra: indexed, watertight where the volume is observed
     depth_from_probe(probe, alpha=None, kind="median" | "expected")       view-space z of a PixelProbe, 0 where there is none
     save_mesh_ply(path, mesh) / load_mesh_ply(path)                       binary little-endian PLY, round trip bit-exact
+    components(mesh) -> Components(vertex_label, face_count)              connected components over vertices
+    compact(mesh, keep_face) -> Mesh                                      faces[keep], unreferenced vertices dropped, indices remapped
+    filter_components(mesh, min_faces=0, keep_largest=None) -> Mesh       2DGS's post_process_mesh(cluster_to_keep): floaters go
+    vertex_normals(mesh) -> [Nv,3]                                        area-weighted, pointing to positive tsdf
+    smooth(mesh, iterations=10, lam=0.5, mu=-0.53) -> Mesh                Taubin smoothing: the voxel staircase goes, the volume stays
 
 Both hot pieces are native (csrc/tsdf.hip): gsr_tsdf_integrate walks all V views inside ONE kernel, so the volume is read and
 written once per call; gsr_mesh_count / gsr_mesh_emit are count -> scan -> emit with one host read of the two counts in between.  include/gsr.h
@@ -17,6 +22,16 @@ states the semantics and the numerics contract; INTEGRATION.md 3n the recipe.  T
         depth = torch.stack([gsr_scene.mesh.depth_from_probe(rasterizer_of(c).probe(...)[0]) for c in cams])
         vol.integrate(depth, cams)
     gsr_scene.mesh.save_mesh_ply("mesh.ply", vol.extract())
+
+The clean-up after the extraction is native too (csrc/meshops.hip):
+
+    m = gsr_scene.mesh.filter_components(vol.extract(), keep_largest=1)   # or min_faces=50
+    m = gsr_scene.mesh.smooth(m, iterations=10)
+    normals = gsr_scene.mesh.vertex_normals(m)
+
+A row of `faces` whose indices are not three different numbers in [0, Nv) is not a face: it joins nothing, counts nowhere and survives no compaction.
+Components are connected through shared VERTICES (two closed surfaces touching in one vertex are one component; Open3D's
+cluster_connected_triangles joins across shared edges and reports two).
 
 The PLY container is written here with numpy: a mesh needs the list property `vertex_indices`, which the in-tree plyfile stand-in refuses."""
 from __future__ import annotations
@@ -244,3 +259,152 @@ def load_mesh_ply(path: str) -> Mesh:
         raise pkg.GsrError(f"load_mesh_ply: {path} has faces that are not triangles")
     colors = torch.from_numpy(vrec["c"].astype(np.float32) / np.float32(255.0)) if has_color else None
     return Mesh(torch.from_numpy(vrec["p"].astype(np.float32)), torch.from_numpy(frec["i"].astype(np.int32)), colors)
+
+
+# ---- clean-up of an extracted mesh (csrc/meshops.hip) ---------------------------------------------------------------------------------------
+class Components(NamedTuple):
+    """vertex_label [Nv] int32: the smallest vertex index of the vertex's component (a vertex no face uses is its own component); face_count [Nv]
+    int32: the faces of the component whose label is the index, 0 at every index that is no label."""
+    vertex_label: torch.Tensor
+    face_count: torch.Tensor
+
+
+def _describe(t) -> str:
+    return f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+
+
+def _checked_mesh(what: str, mesh):
+    """-> (vertices, faces, colors) contiguous, after the shape / dtype / device checks every clean-up call shares."""
+    pkg = _pkg()
+    try:
+        v, f, c = mesh.vertices, mesh.faces, mesh.colors
+    except AttributeError:
+        raise pkg.GsrError(f"{what}: expected a Mesh(vertices, faces, colors), got {type(mesh).__name__}")
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise pkg.GsrError(f"{what}: vertices must be a float32 tensor of shape [Nv,3], got {_describe(v)}")
+    if not torch.is_tensor(f) or f.dtype != torch.int32 or f.dim() != 2 or f.shape[1] != 3:
+        raise pkg.GsrError(f"{what}: faces must be an int32 tensor of shape [Nf,3], got {_describe(f)}")
+    if c is not None and (not torch.is_tensor(c) or c.dtype != torch.float32 or tuple(c.shape) != tuple(v.shape)):
+        raise pkg.GsrError(f"{what}: colors must be None or a float32 tensor of shape {tuple(v.shape)}, got {_describe(c)}")
+    pkg._require_cuda(v, "vertices")
+    for name, t in (("faces", f), ("colors", c)):
+        if t is not None and t.device != v.device:
+            raise pkg.GsrError(f"{what}: {name} on {t.device}, vertices on {v.device}")
+    if 3 * int(f.shape[0]) >= 2 ** 31:
+        raise pkg.GsrError(f"{what}: {int(f.shape[0])} faces have 2^31 or more corners")
+    return v.contiguous(), f.contiguous(), (c.contiguous() if c is not None else None)
+
+
+def _meshops_scratch(lib, nv: int, nf: int, device) -> torch.Tensor:
+    nbytes = int(lib.gsr_meshops_scratch_bytes(nv, nf))
+    scratch = torch.empty(nbytes + 128, dtype=torch.uint8, device=device)
+    return scratch[(-scratch.data_ptr()) % 128:]
+
+
+@torch.no_grad()
+def components(mesh) -> Components:
+    """Connected components over vertices (two vertices are connected when a face holds both).  The call synchronises the mesh's stream: the
+    host reads one word per round of the labelling."""
+    pkg = _pkg()
+    v, f, _ = _checked_mesh("components", mesh)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    lib = pkg._lib.load()
+    label = torch.empty(nv, dtype=torch.int32, device=v.device)
+    count = torch.empty(nv, dtype=torch.int32, device=v.device)
+    scratch = _meshops_scratch(lib, nv, nf, v.device)
+    with torch.cuda.device(v.device):
+        pkg._lib.check(lib.gsr_mesh_components(nv, nf, pkg._ptr(f), pkg._ptr(label), pkg._ptr(count), pkg._ptr(scratch), pkg._stream_ptr(v.device)),
+                       f"gsr_mesh_components ({nv} vertices, {nf} faces)")
+    return Components(label, count)
+
+
+def _compact(what: str, v, f, c, keep) -> Mesh:
+    pkg = _pkg()
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    lib = pkg._lib.load()
+    scratch = _meshops_scratch(lib, nv, nf, v.device)
+    counts = torch.empty(2, dtype=torch.int32, device=v.device)
+    with torch.cuda.device(v.device):
+        stream = pkg._stream_ptr(v.device)
+        pkg._lib.check(lib.gsr_mesh_compact_count(nv, nf, pkg._ptr(f), pkg._ptr(keep), pkg._ptr(scratch), pkg._ptr(counts), stream),
+                       f"gsr_mesh_compact_count ({nv} vertices, {nf} faces)")
+        nv2, nf2 = (int(x) for x in counts.tolist())      # the one synchronisation
+        vertices = torch.empty((nv2, 3), dtype=torch.float32, device=v.device)
+        faces = torch.empty((nf2, 3), dtype=torch.int32, device=v.device)
+        colors = torch.empty((nv2, 3), dtype=torch.float32, device=v.device) if c is not None else None
+        pkg._lib.check(lib.gsr_mesh_compact_emit(nv, nf, pkg._ptr(v), pkg._ptr(c), pkg._ptr(f), pkg._ptr(keep), pkg._ptr(scratch), nv2, nf2,
+                                                 pkg._ptr(vertices), pkg._ptr(colors), pkg._ptr(faces), stream),
+                       f"gsr_mesh_compact_emit ({nv} -> {nv2} vertices, {nf} -> {nf2} faces)")
+    return Mesh(vertices, faces, colors)
+
+
+@torch.no_grad()
+def compact(mesh, keep_face) -> Mesh:
+    """The faces with keep_face[f] set (a [Nf] bool or uint8 tensor; None keeps every face), the vertices they use, indices remapped; both keep
+    their relative order.  Rows that are no faces never survive.  One host read (the two counts)."""
+    pkg = _pkg()
+    v, f, c = _checked_mesh("compact", mesh)
+    keep = keep_face
+    if keep is not None:
+        if not torch.is_tensor(keep) or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (int(f.shape[0]),):
+            raise pkg.GsrError(f"compact: keep_face must be a bool or uint8 tensor of shape ({int(f.shape[0])},), got {_describe(keep)}")
+        if keep.device != v.device:
+            raise pkg.GsrError(f"compact: keep_face on {keep.device}, vertices on {v.device}")
+        keep = keep.contiguous().view(torch.uint8) if keep.dtype == torch.bool else keep.contiguous()
+    return _compact("compact", v, f, c, keep)
+
+
+@torch.no_grad()
+def filter_components(mesh, min_faces: int = 0, keep_largest: Optional[int] = None) -> Mesh:
+    """2DGS's post_process_mesh rule: keeps the faces of every component with at least max(min_faces, the keep_largest-th largest component's
+    face count) faces -- ties at the threshold are all kept -- and the vertices they use.  The threshold and the mask are a few torch
+    operations on the device; labelling and compaction are native."""
+    pkg = _pkg()
+    if keep_largest is not None and int(keep_largest) < 1:
+        raise pkg.GsrError(f"filter_components: keep_largest must be None or >= 1, got {keep_largest}")
+    v, f, c = _checked_mesh("filter_components", mesh)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    if nv == 0 or nf == 0:
+        return _compact("filter_components", v, f, c, None)
+    label, count = components(Mesh(v, f, None))
+    threshold = torch.full((), int(min_faces), dtype=torch.int32, device=v.device)
+    if keep_largest is not None:      # (indices that are no label hold 0: more components asked for than there are keeps every face)
+        threshold = torch.maximum(threshold, torch.topk(count, min(int(keep_largest), nv)).values[-1])
+    first = f[:, 0].long()
+    safe = torch.where((first >= 0) & (first < nv), first, torch.zeros_like(first))      # (a row that is no face is dropped by the compaction)
+    keep = (count[label[safe].long()] >= threshold).view(torch.uint8)
+    return _compact("filter_components", v, f, c, keep)
+
+
+@torch.no_grad()
+def vertex_normals(mesh) -> torch.Tensor:
+    """[Nv,3] float32 unit normals, area-weighted (the sum of the incident faces' cross products, in fp64), pointing to positive tsdf for a mesh
+    of TSDFVolume.extract; (0,0,0) at a vertex without a face or with a zero sum."""
+    pkg = _pkg()
+    v, f, _ = _checked_mesh("vertex_normals", mesh)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    lib = pkg._lib.load()
+    out = torch.empty((nv, 3), dtype=torch.float32, device=v.device)
+    scratch = _meshops_scratch(lib, nv, nf, v.device)
+    with torch.cuda.device(v.device):
+        pkg._lib.check(lib.gsr_mesh_vertex_normals(nv, nf, pkg._ptr(v), pkg._ptr(f), pkg._ptr(out), pkg._ptr(scratch), pkg._stream_ptr(v.device)),
+                       f"gsr_mesh_vertex_normals ({nv} vertices, {nf} faces)")
+    return out
+
+
+@torch.no_grad()
+def smooth(mesh, iterations: int = 10, lam: float = 0.5, mu: float = -0.53) -> Mesh:
+    """Taubin smoothing: `iterations` times a step towards the neighbours' mean with weight lam, then one with weight mu (negative: it undoes the
+    shrinkage).  A neighbour weighs by the faces on the edge to it (include/gsr.h).  Faces and colours are carried over, the input is not written."""
+    pkg = _pkg()
+    v, f, c = _checked_mesh("smooth", mesh)
+    if int(iterations) < 0:
+        raise pkg.GsrError(f"smooth: iterations must be >= 0, got {iterations}")
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    lib = pkg._lib.load()
+    out = torch.empty((nv, 3), dtype=torch.float32, device=v.device)
+    scratch = _meshops_scratch(lib, nv, nf, v.device)
+    with torch.cuda.device(v.device):
+        pkg._lib.check(lib.gsr_mesh_smooth(nv, nf, pkg._ptr(v), pkg._ptr(f), int(iterations), float(lam), float(mu), pkg._ptr(out), pkg._ptr(scratch),
+                                           pkg._stream_ptr(v.device)), f"gsr_mesh_smooth ({nv} vertices, {nf} faces, {iterations} iterations)")
+    return Mesh(out, f, c)

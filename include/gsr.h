@@ -868,6 +868,64 @@ int gsr_mesh_emit(int nx, int ny, int nz, float ox, float oy, float oz, float vo
                   void* scratch, int nv, int nf, float* vertices, float* colors_or_null, int32_t* faces, void* stream);
 
 /*
+ * Mesh clean-up on an indexed triangle mesh -- what 2DGS's post_process_mesh(cluster_to_keep) and its kin in GOF, RaDe-GS and PGSR run before a
+ * mesh is saved or evaluated: connected components, removal of small clusters, vertex normals, Taubin smoothing.  gsr_scene/mesh.py is the
+ * package side (components, compact, filter_components, vertex_normals, smooth).  (Additive, the ABI version stays 4.)
+ *
+ * THE RULE every call shares: row f of faces [nf,3] (int32) is a FACE iff its three indices are in [0, nv) and pairwise different.  Any other
+ * row is not there: no kernel reads a vertex through it, it joins nothing, it counts nowhere and it survives no compaction.
+ * Sizes: 0 <= nv < 2^31, 0 <= 3 nf < 2^31, anything else is GSR_ERR_INVALID_ARG; empty inputs are valid calls that write nothing
+ * (gsr_mesh_compact_count writes the two zeros).  scratch: gsr_meshops_scratch_bytes(nv, nf) bytes, 128-byte aligned, caller-owned, one
+ * layout for all five operations; its contents need not be initialised, and a call reads only what it (or, for the emit, the count before
+ * it) wrote.  No floating-point atomics anywhere: two runs give the same bits.
+ *
+ * gsr_mesh_components: two vertices are connected when a face holds both (connectivity is by VERTEX: two closed surfaces that share one
+ * vertex are one component, where Open3D's cluster_connected_triangles, which joins triangles across shared edges, reports two).
+ * vertex_label[v] (int32 [nv]) = the smallest vertex index of v's component; a vertex no face uses is its own component.  face_count[r]
+ * (int32 [nv]) = the number of faces of the component whose label is r, 0 at every v that is no label.  Rounds of hook (per face and edge,
+ * an integer atomicMin of the smaller of the two ends' current labels into the slot of the larger) and compress (every vertex points at its
+ * root); labels only fall and stay inside the component, so the fixpoint is the component's minimum whatever the schedule.  The host reads
+ * one word per round and stops at a round that hooked nothing: THE CALL SYNCHRONISES THE STREAM.  More than 2 ceil(log2(nv + 1)) + 8 rounds
+ * is GSR_ERR_UNSUPPORTED (the call never spins); gsr_mesh_components_rounds() returns the rounds of the most recent call.
+ *
+ * gsr_mesh_compact_count / _emit: keep_face [nf] (uint8, non-zero = keep; NULL = keep every face) selects faces; a vertex is kept iff a kept
+ * face uses it.  The count leaves {nv', nf'} in counts_out (int32 [2], device); the caller reads them -- the one synchronisation --
+ * allocates, and the emit writes vertices' [nv',3], colors' [nv',3] (with colors; both or neither) and faces' [nf',3] from the SAME
+ * scratch, faces and keep_face.  Kept vertices and kept faces stay in their original relative order and the indices are remapped: the
+ * output is faces[keep] with new index = (number of kept vertices before it), values copied bit for bit.  Nothing is written past nv_out
+ * vertices or nf_out faces; nv_out == 0 succeeds without a launch.
+ *
+ * gsr_mesh_vertex_normals: area-weighted.  N_i = sum over the faces f that hold vertex i, in ascending f, of (b - a) x (c - a) with
+ * (a, b, c) the face's own corner order; every operand is converted to fp64 first, the cross product is (uy wz - uz wy, uz wx - ux wz,
+ * ux wy - uy wx) and the sum runs in fp64.  n_i = N_i / sqrt((Nx Nx + Ny Ny) + Nz Nz) in fp64, rounded once to fp32; N_i == 0 exactly, or
+ * no face, gives (0,0,0).  With gsr_mesh_emit's winding the normal points to positive tsdf (outside).  Non-finite positions give whatever
+ * IEEE arithmetic yields, and only at the vertices of the faces that hold them.
+ *
+ * gsr_mesh_smooth: Taubin smoothing, `iterations` times a step with weight lambda followed by a step with weight mu (Taubin 1995: lambda > 0,
+ * mu < -lambda; 0.5 / -0.53 are the customary pair).  One step with weight w, F_i the faces that hold vertex i in ascending order:
+ *   S = sum over f in F_i of (p_j + p_k), j, k the two corners after i in f's cyclic order;   m = S / (2 |F_i|);   p_i' = p_i + w (m - p_i),
+ * all in fp64 on operands converted first, rounded once to fp32; a vertex with |F_i| = 0 keeps its bits.  The weight of a neighbour in m is
+ * therefore the number of faces on the edge to it: 2 on closed manifold regions, where every neighbour weighs the same and the step is
+ * exactly the uniform umbrella operator, and 1 across a boundary edge.  All 2 iterations launches go out in one call, ping-pong between the
+ * scratch and vertices_out; the input is never written (vertices_out must be another buffer).  iterations == 0 copies.  A non-finite
+ * position reaches only vertices within 2 iterations edges of it.  NaN weights and iterations < 0 are GSR_ERR_INVALID_ARG.
+ * The incident-face lists of the last two calls are the corners (vertex id, 3 f + k) sorted by vertex with the stable pair sort of the
+ * binning chain, so a vertex's corners come out in ascending face order.
+ */
+size_t gsr_meshops_scratch_bytes(int nv, int nf);            /* 0: unsupported sizes */
+int gsr_mesh_components(int nv, int nf, const int32_t* faces, int32_t* vertex_label, int32_t* face_count, void* scratch,
+                        void* stream);                       /* synchronises the stream */
+int gsr_mesh_components_rounds(void);                        /* hook + compress rounds of the most recent gsr_mesh_components */
+int gsr_mesh_compact_count(int nv, int nf, const int32_t* faces, const uint8_t* keep_face_or_null, void* scratch,
+                           int32_t* counts_out /*[2]: nv', nf'*/, void* stream);
+int gsr_mesh_compact_emit(int nv, int nf, const float* vertices, const float* colors_or_null, const int32_t* faces,
+                          const uint8_t* keep_face_or_null, void* scratch, int nv_out, int nf_out, float* vertices_out,
+                          float* colors_out_or_null, int32_t* faces_out, void* stream);
+int gsr_mesh_vertex_normals(int nv, int nf, const float* vertices, const int32_t* faces, float* normals_out, void* scratch, void* stream);
+int gsr_mesh_smooth(int nv, int nf, const float* vertices, const int32_t* faces, int iterations, float lambda, float mu,
+                    float* vertices_out, void* scratch, void* stream);
+
+/*
  * Replaces `simple_knn._C.distCUDA2` (un-vendored submodule submodules/simple-knn, .gitmodules:1-3; called once per
  * scene at scene/gaussian_model.py:159): mean_dist2[i] = mean of the squared Euclidean distances
  * from points[i] to its 3 nearest OTHER points (exact; coincident points count with distance 0; fewer than 4 points

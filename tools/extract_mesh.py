@@ -3,13 +3,17 @@ surface by marching tetrahedra and write mesh.ply (gsr_scene.mesh; INTEGRATION.m
 
     python tools/extract_mesh.py [--ply point_cloud.ply] [--cameras cameras.npy] [--views 48] [--image 540x960] [--resolution 256]
                                  [--trunc-voxels 4] [--depth median|expected] [--min-weight 2] [--save-cameras used.npy] [--out mesh.ply]
+                                 [--keep-largest N] [--min-faces N] [--smooth K]
 
 Without --ply the scene is synthetic: Gaussians on a sphere.  Cameras: --cameras takes the training views as packed records, a [V,16] float
 array in a .npy file or a tensor in a .pt file -- what gsr_scene.mip.pack_cameras(scene.getTrainCameras(), "cpu") returns: R[9] row-major and
 T[3] with cam = xyz R + T, focal_x, focal_y, width, height; all of one size, the principal point in the centre.  Without it the views are a
 synthetic orbit (gsr_synth.look_at_camera) around the centre of the point cloud at --orbit times its extent, of --views views of --image.
 --save-cameras writes the records that were used.  The volume is the cloud's central bounding box (the 1 % .. 99 % quantiles, enlarged by 10 %),
---resolution voxels along its longest side."""
+--resolution voxels along its longest side.
+Clean-up (all off by default, the mesh is then the raw extraction): --keep-largest N and --min-faces N keep the faces of the
+components with at least max(min-faces, the N-th largest component's face count) faces (2DGS's post_process_mesh; floaters go), --smooth K applies K
+Taubin iterations (the voxel staircase goes).  With any of them the vertices and faces before and after are printed."""
 import argparse
 import math
 import os
@@ -40,6 +44,9 @@ ap.add_argument("--depth", default="median", choices=["median", "expected"])
 ap.add_argument("--min-weight", type=float, default=2.0)
 ap.add_argument("--batch", type=int, default=16, help="views per integrate call")
 ap.add_argument("--out", default="mesh.ply")
+ap.add_argument("--keep-largest", type=int, default=None, help="keep the N largest connected components (ties at the threshold stay)")
+ap.add_argument("--min-faces", type=int, default=0, help="drop connected components with fewer faces")
+ap.add_argument("--smooth", type=int, default=0, help="Taubin smoothing iterations (lambda 0.5, mu -0.53)")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("extract_mesh.py: no HIP device")
@@ -121,6 +128,14 @@ for v in range(records.shape[0]):
         depths = []
 observed = float((volume.weight >= args.min_weight).float().mean())
 m = volume.extract(args.min_weight)
+if args.keep_largest is not None or args.min_faces > 0 or args.smooth > 0:
+    before = (m.vertices.shape[0], m.faces.shape[0])
+    if args.keep_largest is not None or args.min_faces > 0:
+        m = mesh.filter_components(m, min_faces=args.min_faces, keep_largest=args.keep_largest)
+    if args.smooth > 0:
+        m = mesh.smooth(m, iterations=args.smooth)
+    parts = int((mesh.components(m).face_count > 0).sum())
+    print(f"clean-up: {before[0]} vertices, {before[1]} faces -> {m.vertices.shape[0]} vertices, {m.faces.shape[0]} faces in {parts} component(s)", flush=True)
 mesh.save_mesh_ply(args.out, m)
 print(f"{observed * 100:.1f} % of the voxels observed by >= {args.min_weight:g} views; wrote {args.out}: {m.vertices.shape[0]} vertices, {m.faces.shape[0]} faces",
       flush=True)
